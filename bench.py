@@ -9,7 +9,7 @@ with no data-path collective (frames are independent units), so scaling is
 weak: every rank encodes its own batch; value = all ranks' pixels / the
 slowest rank's wall time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Either launch works: without a launcher, `--gpus N` starts N rank processes
@@ -18,9 +18,15 @@ the barrier and the max over ranks through a small TCP group on the host
 (vcf_amd/comm.py).
 
 Rank 0 prints one JSON line.  The roofline block is measured live with HIP
-events on the stream the kernel runs on; the cpu_baseline block times the
-reference's CPU path restated in numpy (oracle/ref_numpy.py) on a bounded
-sample of the same frames, beside the C port of the oracle.
+events on the stream the kernel runs on, over the timed steps themselves.
+
+A plain run does only what the headline needs: set up, warm up and settle,
+time the steps, write the outputs (--dump-outputs) and print the line.
+Everything else runs only with --full, after the headline's timed region: the
+C4 / C5 / C3 / C2 config blocks, the parity check of the timed kernel's output
+against the oracle, and the cpu_baseline blocks, which time the reference's
+CPU path restated in numpy (oracle/ref_numpy.py) on a bounded sample of the
+same frames, beside the C port of the oracle.
 """
 from __future__ import annotations
 
@@ -826,10 +832,51 @@ def load_traffic(workload: str):
     return d.get("hbm_bytes_per_launch"), os.path.relpath(p, ROOT)
 
 
+DUMP_ELEMS = 8 << 20     # --dump-outputs: at most this many indices (32 MB as float32)
+DUMP_SEED = 20240607     # the sample's positions are the same in every run
+
+
+def dump_positions(F: int, frame_elems: int):
+    """Positions (within one frame's index array) that --dump-outputs keeps of
+    every frame: all of them while F frames fit DUMP_ELEMS, else a fixed
+    seeded sample, sorted, the same for every frame and every run."""
+    per = max(1, DUMP_ELEMS // max(F, 1))
+    if per >= frame_elems:
+        return None
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    return np.sort(rng.choice(frame_elems, per, replace=False))
+
+
+def dump_outputs(path: str, dout, F: int, frame_elems: int) -> dict:
+    """Write what the last timed step left in `dout` (the u8 deadzone indices
+    vcf_dct_dz_encode returns, F frames of Hp x Wp x 3 in subband layout) as
+    path/dct_dz_indices.npy: float32, shape (F, n), n = the whole frame or
+    dump_positions()'s sample of it.  Frame by frame, so the host never holds
+    more than one frame beside the sample."""
+    os.makedirs(path, exist_ok=True)
+    pos = dump_positions(F, frame_elems)
+    n = frame_elems if pos is None else pos.size
+    out = np.empty((F, n), np.float32)
+    frame = np.empty(frame_elems, np.uint8)
+    for f in range(F):
+        dout.download(frame, offset=f * frame_elems)
+        out[f] = frame if pos is None else frame[pos]
+    fn = os.path.join(path, "dct_dz_indices.npy")
+    np.save(fn, out)
+    return {"files": ["dct_dz_indices.npy"], "shape": [F, n], "dtype": "float32",
+            "sample": "every index" if pos is None else f"{n} of {frame_elems} positions per frame, PCG64({DUMP_SEED})"}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output (rank 0's index frames, or a fixed "
+                         "seeded sample of them) as DIR/dct_dz_indices.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the C4 / C5 / C3 / C2 config blocks, the parity check "
+                         "against the oracle and the CPU baselines (the options below them apply only then)")
     ap.add_argument("--warmup", type=int, default=50, help="untimed steps before the settle phase")
     ap.add_argument("--settle-min-s", type=float, default=1.5,
                     help="after --warmup, keep warming up at least this long and until launch times are "
@@ -857,6 +904,8 @@ def main():
     ap.add_argument("--c2-reps", type=int, default=5, help="encode_fn/decode_fn calls per codec of the C2 block "
                                                         "(0 disables it)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -909,24 +958,29 @@ def main():
     pixels = group.allreduce_sum(float(args.steps * F * H * W))
     value = pixels / wall_max / 1e6
 
+    # what the last timed step computed (rank 0's frames), before anything else runs
+    dumped = dump_outputs(args.dump_outputs, dout, F, Hp * Wp * 3) if args.dump_outputs and rank == 0 else None
+
+    # everything below the headline runs only with --full
+    full = args.full
     # C4 (III, 256 x 1080p, frame-sharded, with the RCCL exchange): after the
     # headline's timed region, reported in its own block
-    c4 = c4_block(args, world, rank, group) if args.c4_frames > 0 else None
+    c4 = c4_block(args, world, rank, group) if full and args.c4_frames > 0 else None
     # the same with the reference's default entropy codec, -c TIFF (GPU deflate)
-    c4t = c4_block(args, world, rank, group, "TIFF") if args.c4_frames > 0 and not args.no_c4_tiff else None
+    c4t = c4_block(args, world, rank, group, "TIFF") if full and args.c4_frames > 0 and not args.no_c4_tiff else None
     # C5 (IPP_DCT, 64 x 4K, GOP 10, full search, -c TIFF on the GPU deflate, GOP-sharded)
-    c5 = c5_block(args, world, rank, group) if args.c5_frames > 0 else None
+    c5 = c5_block(args, world, rank, group) if full and args.c5_frames > 0 else None
     # C3 (2D-DWT l=5 bior4.4 + deadzone, 8 x 4K per rank, HBM-resident) and C2
     # (one 1080p PNG through encode_fn/decode_fn with -c CBAAC and -c TCBAACP)
-    c3 = c3_block(args, world, rank, group, distinct) if args.c3_steps > 0 else None
-    c2 = c2_block(args, world, rank, group) if args.c2_reps > 0 else None
+    c3 = c3_block(args, world, rank, group, distinct) if full and args.c3_steps > 0 else None
+    c2 = c2_block(args, world, rank, group) if full and args.c2_reps > 0 else None
 
     # after the timed region (an idle GPU during seconds of CPU work would start
     # the timed steps at low clocks): parity spot check of the timed kernel's
     # output, frame 0 vs the C oracle, and the CPU baseline
     parity = None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, k_ref = cpu_baseline(distinct[0], Q, args.cpu_budget)
         k_gpu = dout.download(np.empty((Hp, Wp, 3), np.uint8))
         parity = "bit-exact vs oracle (frame 0)" if np.array_equal(k_gpu, k_ref) else "MISMATCH"
@@ -980,14 +1034,20 @@ def main():
                          "read_bytes_per_launch": F * H * W * 3,
                          "read_GBps": round(F * H * W * 3 / (kernel_ms * 1e-3) / 1e9, 1),
                          "read_frac_of_peak": round(F * H * W * 3 / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-            "cpu_baseline": cpu,
-            "parity": parity,
-            "c4_e2e_with_gather": c4,
-            "c4_tiff_e2e_with_gather": c4t,
-            "c5_e2e_with_gather": c5,
-            "c3_dwt": c3,
-            "c2_encode_decode_fn": c2,
+            "full": full,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if full:
+            out.update({
+                "cpu_baseline": cpu,
+                "parity": parity,
+                "c4_e2e_with_gather": c4,
+                "c4_tiff_e2e_with_gather": c4t,
+                "c5_e2e_with_gather": c5,
+                "c3_dwt": c3,
+                "c2_encode_decode_fn": c2,
+            })
         print(json.dumps(out), flush=True)
     group.close()
 

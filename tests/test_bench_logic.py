@@ -35,3 +35,17 @@ def test_c3_fp64_op_count():
     import bench
     assert abs(bench.c3_fp64_ops_per_pixel() - 90 * sum(0.25 ** l for l in range(5))) < 1e-9
     assert abs(bench.c3_fp64_ops_per_pixel(levels=1) - 90.0) < 1e-9
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: whole frames while they fit the budget, else the same
+    sorted, seeded positions in every run; never more than 64 MB as float32."""
+    import numpy as np
+
+    import bench
+    assert bench.dump_positions(3, 72 * 104 * 3) is None
+    fe = 2160 * 3840 * 3
+    a, b = bench.dump_positions(64, fe), bench.dump_positions(64, fe)
+    assert np.array_equal(a, b) and a.size == bench.DUMP_ELEMS // 64
+    assert np.all(np.diff(a) > 0) and 0 <= a[0] and a[-1] < fe
+    assert 64 * a.size * 4 <= 64 << 20

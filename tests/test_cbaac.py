@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from golden_io import load_npz
 from vcf_amd import cbaac as C
 
 _MAN = json.load(open(os.path.join(GOLDEN, "manifest_cbaac.json")))
@@ -19,7 +20,7 @@ _MAN = json.load(open(os.path.join(GOLDEN, "manifest_cbaac.json")))
 
 @pytest.mark.parametrize("case", _MAN["cases"], ids=lambda c: f"{c['stream']}_o{c['order']}")
 def test_model_trace_equals_reference(case):
-    d = np.load(os.path.join(GOLDEN, "cbaac_model.npz"))
+    d = load_npz(os.path.join(GOLDEN, "cbaac_model.npz"))
     sym = d[f"sym_{case['stream']}"]
     ref = d[f"trace_{case['stream']}_o{case['order']}"]
     got = C.model_trace(sym, case["order"])

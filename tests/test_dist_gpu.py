@@ -129,7 +129,7 @@ def test_bench_two_ranks_without_launcher():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "4",
-                        "--steps", "3", "--warmup", "1", "--settle-max-s", "0", "--no-cpu-baseline"],
+                        "--steps", "3", "--warmup", "1", "--settle-max-s", "0", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -148,7 +148,7 @@ def test_bench_two_ranks_under_torchrun():
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
                         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "4", "--steps", "3",
-                        "--warmup", "1", "--settle-max-s", "0", "--no-cpu-baseline"],
+                        "--warmup", "1", "--settle-max-s", "0", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
@@ -215,7 +215,7 @@ def test_bench_c4_block_small():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "2", "--steps", "2",
-                        "--warmup", "1", "--settle-max-s", "0", "--no-cpu-baseline", "--c4-frames", "6"],
+                        "--warmup", "1", "--settle-max-s", "0", "--full", "--no-cpu-baseline", "--c4-frames", "6"],
                        env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])

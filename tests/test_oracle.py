@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, case_params, golden_cases, load_case
+from golden_io import load_npz
 from oracle import oracle as O
 
 
@@ -63,7 +64,7 @@ def test_oracle_512_cases_by_hash(manifest, name):
 
 
 def test_oracle_blocks_vs_pocketfft():
-    b = np.load(os.path.join(GOLDEN, "blocks.npz"))
+    b = load_npz(os.path.join(GOLDEN, "blocks.npz"))
     # forward: axis 0 (columns) then axis 1 (rows), fp32
     x = b["fwd_in"]
     cols = O.dct2_8(np.swapaxes(x, 1, 2), np.float32)          # transform each column

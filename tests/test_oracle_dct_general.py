@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from golden_io import load_npz
 from oracle import oracle as O
 
 MANIFEST = json.load(open(os.path.join(GOLDEN, "manifest_general.json")))
@@ -39,7 +40,7 @@ def _qf(flags):
 
 @pytest.mark.parametrize("N", MANIFEST["lengths"])
 def test_oracle_dct_lengths_vs_scipy(N):
-    g = np.load(os.path.join(GOLDEN, "blocks_general.npz"))
+    g = load_npz(os.path.join(GOLDEN, "blocks_general.npz"))
     assert O.dct_supported(N)
     fwd = O.dct_n(g[f"fwd_in_{N}"], 2, np.float32)
     assert fwd.dtype == g[f"fwd_out_{N}"].dtype == np.float32
@@ -55,7 +56,7 @@ RADG = json.load(open(os.path.join(GOLDEN, "manifest_radg.json")))
 def test_oracle_dct_radfg_radbg_lengths_vs_scipy(N):
     """Lengths with a prime factor above 5 (pocketfft's generic radfg/radbg),
     against scipy.fftpack under the reference's python (make_golden_radg.py)."""
-    g = np.load(os.path.join(GOLDEN, "blocks_radg.npz"))
+    g = load_npz(os.path.join(GOLDEN, "blocks_radg.npz"))
     assert O.dct_supported(N)
     fwd = O.dct_n(g[f"fwd_in_{N}"], 2, np.float32)
     assert np.array_equal(fwd.view(np.uint32), g[f"fwd_out_{N}"].view(np.uint32))
@@ -84,7 +85,7 @@ def test_oracle_cfft_vs_scipy():
     padded length the Bluestein plans of N <= 600 use, plus small lengths that
     exercise each pass; ifft with norm='forward' is the unnormalised backward
     pass."""
-    g = np.load(os.path.join(GOLDEN, "cfft_blue.npz"))
+    g = load_npz(os.path.join(GOLDEN, "cfft_blue.npz"))
     for N in BLUE["cfft_lengths"]:
         for nm in ("c64", "c128"):
             x = g[f"x_{nm}_{N}"]
@@ -100,7 +101,7 @@ def test_oracle_cfft_vs_scipy():
 def test_oracle_dct_bluestein_blocks_vs_scipy(N):
     """DCT-II/III of the Bluestein lengths (fftblue::exec_r inside T_dcst23)
     against scipy.fftpack under the reference's python, bit for bit."""
-    g = np.load(os.path.join(GOLDEN, "blocks_blue.npz"))
+    g = load_npz(os.path.join(GOLDEN, "blocks_blue.npz"))
     fwd = O.dct_n(g[f"fwd_in_{N}"], 2, np.float32)
     assert np.array_equal(fwd.view(np.uint32), g[f"fwd_out_{N}"].view(np.uint32))
     inv = O.dct_n(g[f"inv_in_{N}"].astype(np.float64), 3, np.float64)

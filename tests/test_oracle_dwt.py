@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from golden_io import load_npz
 from oracle import oracle as O
 
 _MAN = json.load(open(os.path.join(GOLDEN, "manifest_dwt.json")))
@@ -27,13 +28,13 @@ def _params(case):
 
 
 def _pywt_tags():
-    d = np.load(os.path.join(GOLDEN, "dwt_pywt.npz"))
+    d = load_npz(os.path.join(GOLDEN, "dwt_pywt.npz"))
     return sorted({m.group(1) for k in d.files for m in [re.match(r"fwd_in_(.*)", k)] if m})
 
 
 @pytest.mark.parametrize("tag", _pywt_tags())
 def test_wavedec2_waverec2_vs_pywt(tag):
-    d = np.load(os.path.join(GOLDEN, "dwt_pywt.npz"))
+    d = load_npz(os.path.join(GOLDEN, "dwt_pywt.npz"))
     wname = tag.split("_")[0]
     L = int(tag.rsplit("_l", 1)[1])
     x = d[f"fwd_in_{tag}"]
@@ -71,7 +72,7 @@ def test_wavelet_table():
 def test_lines_shorter_than_the_filter_vs_pywt():
     """pywt's short-input branch: idwt/dwt of every line length 1 .. F/2 + 3 for all
     106 discrete wavelets, bit for bit (dwt_short_pywt.npz, make_golden_dwt_short.py)."""
-    d = np.load(os.path.join(GOLDEN, "dwt_short_pywt.npz"))
+    d = load_npz(os.path.join(GOLDEN, "dwt_short_pywt.npz"))
     names = [str(n) for n in d["names"]]
     assert len(names) == 106
     n = 0

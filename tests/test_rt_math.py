@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from golden_io import load_npz
 from oracle import oracle as O
 
 SRC = os.path.join(ROOT, "tests", "cpu", "rt_harness.hip")
@@ -57,7 +58,7 @@ def test_plan_choice_matches_pocketfft(rt):
 def test_bluestein_blocks_vs_scipy(rt):
     """All 67 Bluestein lengths <= 600 against scipy.fftpack dct/idct (ortho)
     under the reference's python (make_golden_blue.py)."""
-    g = np.load(os.path.join(GOLDEN, "blocks_blue.npz"))
+    g = load_npz(os.path.join(GOLDEN, "blocks_blue.npz"))
     for N in BLUE["bluestein_lengths"]:
         fwd = _dct(rt, 2, g[f"fwd_in_{N}"], np.float32)
         assert np.array_equal(fwd.view(np.uint32), g[f"fwd_out_{N}"].view(np.uint32)), N
@@ -68,7 +69,7 @@ def test_bluestein_blocks_vs_scipy(rt):
 def test_rfftp_blocks_vs_scipy(rt):
     """The rfftp lengths (radfg/radbg included) of blocks_radg.npz."""
     radg = json.load(open(os.path.join(GOLDEN, "manifest_radg.json")))
-    g = np.load(os.path.join(GOLDEN, "blocks_radg.npz"))
+    g = load_npz(os.path.join(GOLDEN, "blocks_radg.npz"))
     for N in radg["lengths"]:
         fwd = _dct(rt, 2, g[f"fwd_in_{N}"], np.float32)
         assert np.array_equal(fwd.view(np.uint32), g[f"fwd_out_{N}"].view(np.uint32)), N

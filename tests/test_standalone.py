@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 from PIL import Image
 
+from golden_io import load_npz
 from oracle import plugins as O
 from vcf_amd.codec import parser as P
 
@@ -26,7 +27,7 @@ def cases(module=None):
 
 
 def load(c):
-    return np.load(os.path.join(GOLD, f"sa_{c['name']}.npz"), allow_pickle=False)
+    return load_npz(os.path.join(GOLD, f"sa_{c['name']}.npz"), allow_pickle=False)
 
 
 def qss(c):
