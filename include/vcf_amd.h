@@ -445,7 +445,8 @@ int64_t vcf_png_encode_bound(int32_t H, int32_t W);
  * tifffile.imwrite(..., compression='zlib') stores per RowsPerStrip strip
  * (TIFF.py:29; host path vcf_amd/codec/tiff.py _deflate_strips).  Frame f is
  * in_dev[f*frame_bytes, (f+1)*frame_bytes), cut into strips of strip_bytes
- * (the last one shorter); strip s = f*spf + k, spf = vcf_zlib_strip_count,
+ * (the last one shorter; in_dev, frame_bytes and strip_bytes need no
+ * alignment); strip s = f*spf + k, spf = vcf_zlib_strip_count,
  * is written to out_dev + s*slot_bytes and its length to sizes_dev[s]
  * (-1: slot too small).  level 4..9 (VCF_ERR_UNSUPPORTED otherwise);
  * strip_bytes <= 65536 (tifffile's strips for rows up to 64 KB);

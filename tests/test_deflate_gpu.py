@@ -250,3 +250,218 @@ def test_many_rounds_every_strip_equals_zlib():
                        timeout=280)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert "bad 0" in p.stdout
+
+
+# ---- the named corpus (tests/deflate_cases.py): both parse paths in one call ----
+# tests/test_deflate.py asserts what the corpus holds (lazy and non-lazy strips,
+# multi-block strips, matches past the lazy parse's LDS window, at MAX_DIST, ...)
+# and that the host restatement of the algorithm codes every entry as zlib does.
+_state = {}
+
+
+def _deflater():
+    """One deflater for the corpus tests: its scratch (and the LDS its kernels
+    leave behind) carries over from one call to the next, as in the product."""
+    from vcf_amd.zlib_gpu import StripDeflater
+    if "deflater" not in _state:
+        _state["deflater"] = StripDeflater()
+    return _state["deflater"]
+
+
+def _want(b: bytes, level: int) -> bytes:
+    """zlib.compress, computed once per (strip, level) for the whole module."""
+    cache = _state.setdefault("want", {})
+    key = (b, level)
+    if key not in cache:
+        cache[key] = zlib.compress(b, level)
+    return cache[key]
+
+
+def _deflate(frame_list, strip_bytes, level, offset=0):
+    """Every strip of equal-length frames (bytes) through one call -> flat list of
+    (label suffix, strip bytes, stream)."""
+    from vcf_amd.device import DeviceBuffer
+    fb = len(frame_list[0])
+    assert all(len(f) == fb for f in frame_list)
+    host = np.zeros(offset + fb * len(frame_list), np.uint8)
+    host[offset:] = np.frombuffer(b"".join(frame_list), np.uint8)
+    d = DeviceBuffer.from_array(host)
+    got = _deflater().deflate_device(d, len(frame_list), fb, strip_bytes, level, offset=offset)
+    d.free()
+    out = []
+    for f, b in enumerate(frame_list):
+        strips = [b[i:i + strip_bytes] for i in range(0, fb, strip_bytes)]
+        assert len(got[f]) == len(strips)
+        out += [((f, k), s, bytes(g)) for k, (s, g) in enumerate(zip(strips, got[f]))]
+    return out
+
+
+def _assert_zlib(result, level, label):
+    """Every strip of a _deflate result equals zlib.compress; the failure names the
+    strips and the first differing token of the first one."""
+    from deflate_cases import describe_mismatch
+    bad = [(label(fk), s, g) for fk, s, g in result if g != _want(s, level)]
+    if bad:
+        name, s, g = bad[0]
+        raise AssertionError(f"level {level}: {len(bad)} of {len(result)} strips differ from zlib: "
+                             f"{[b[0] for b in bad[:12]]}; first ({name}, {len(s)} bytes): "
+                             f"{describe_mismatch(g, _want(s, level))}")
+
+
+def _corpus_call(length, level):
+    """The corpus entries of one length as the frames of one call (one strip each)."""
+    from deflate_cases import corpus_by_length
+    entries = corpus_by_length()[length]
+    res = _deflate([b for _, b in entries], length, level)
+    return entries, res
+
+
+@pytest.mark.parametrize("level", [6, 9, 4, 5, 7, 8])
+def test_corpus_equals_zlib(level):
+    """Every corpus entry at this level: the 64 KiB entries (19 lazy, 11 non-lazy
+    by K1's rule) side by side in one call, the other lengths in a call each."""
+    from deflate_cases import corpus, corpus_by_length
+    seen = 0
+    for length in corpus_by_length():
+        entries, res = _corpus_call(length, level)
+        _assert_zlib(res, level, lambda fk: entries[fk[0]][0])
+        seen += len(res)
+    assert seen == len(corpus())
+
+
+def _assert_parse_info(strips, labels, want_listed=None):
+    """The kernel's parse order and distinct count of the last call against
+    lazy_rule's; -> (lazy strips, non-lazy strips)."""
+    from deflate_cases import lazy_rule
+    info = _deflater().parse_info()
+    rule = [lazy_rule(s) for s in strips]
+    bad = [(labels[i], rule[i], int(info["distinct"][i]), bool(info["lazy"][i])) for i in range(len(strips))
+           if rule[i][0] != info["distinct"][i] or rule[i][2] != info["lazy"][i]]
+    assert not bad, bad[:10]
+    n_lazy = sum(r[2] for r in rule)
+    assert info["listed"] == len(strips) - n_lazy, (info["listed"], len(strips), n_lazy)
+    return n_lazy, len(strips) - n_lazy
+
+
+def test_corpus_takes_the_path_it_was_written_for():
+    """K1's parse order word and distinct count of every strip (read back from the
+    workspace, StripDeflater.parse_info) equal the host rule the corpus properties
+    are asserted with, and K1's list of non-lazy strips has their number: the
+    64 KiB call runs at least 10 strips through each parse."""
+    from deflate_cases import STRIP, corpus_by_length
+    for length in corpus_by_length():
+        entries, res = _corpus_call(length, 6)
+        n_lazy, n_non = _assert_parse_info([s for _, s, _ in res], [e[0] for e in entries])
+        print(f"length {length}: {n_lazy} lazy, {n_non} non-lazy")
+        if length == STRIP:
+            assert n_lazy >= 10 and n_non >= 10, (n_lazy, n_non)
+
+
+@pytest.mark.parametrize("tail", [1, 2, 3])
+def test_long_side_lists(tail):
+    """More than 4 096 non-lazy strips in one round: the side kernels' grids
+    (256 / 128 / 4 096 workgroups) wrap around K1's list, with 320 lazy strips
+    interleaved and a last strip of 1, 2 or 3 bytes."""
+    from deflate_cases import small_strip_frame
+    frame = small_strip_frame(272, 4500, 320, tail)
+    res = _deflate([frame], 272, 6)
+    assert len(res) == 4821 and len(res[-1][1]) == tail
+    _assert_zlib(res, 6, lambda fk: f"strip {fk[1]}")
+    n_lazy, n_non = _assert_parse_info([s for _, s, _ in res], list(range(len(res))))
+    print(f"tail {tail}: {n_lazy} lazy, {n_non} non-lazy (K1's list)")
+    assert n_non > 4096 and n_lazy >= 300, (n_lazy, n_non)
+
+
+@pytest.mark.parametrize("level", [6, 9, 4])
+def test_side_list_of_two_chunk_strips(level):
+    """300 non-lazy strips of 5 000 bytes (two K2a chunks each, a K2b worklist split
+    over 4 workgroups) on grids of 256 / 128, 60 lazy strips interleaved."""
+    from deflate_cases import small_strip_frame
+    res = _deflate([small_strip_frame(5000, 300, 60)], 5000, level)
+    _assert_zlib(res, level, lambda fk: f"strip {fk[1]}")
+    n_lazy, n_non = _assert_parse_info([s for _, s, _ in res], list(range(len(res))))
+    assert n_non >= 290 and n_lazy >= 50, (n_lazy, n_non)
+
+
+_ROUNDS = r'''
+import sys, zlib
+import numpy as np
+sys.path[:0] = [sys.argv[1], sys.argv[2]]
+from deflate_cases import STRIP, corpus_by_length, describe_mismatch, lazy_rule, small_strip_frame
+from vcf_amd.device import DeviceBuffer
+from vcf_amd.zlib_gpu import StripDeflater, workspace
+calls = [("corpus", [b for _, b in corpus_by_length()[STRIP]], STRIP),
+         ("5000", [small_strip_frame(5000, 300, 60)], 5000)]
+dfl = StripDeflater()
+for what, frames, sb in calls:
+    strips = [f[i:i + sb] for f in frames for i in range(0, len(f), sb)]
+    per = workspace(len(strips)) // workspace(1)
+    rounds = -(-len(strips) // per)
+    n_lazy = sum(lazy_rule(s)[2] for s in strips)
+    d = DeviceBuffer.from_array(np.frombuffer(b"".join(frames), np.uint8))
+    got = [g for f in dfl.deflate_device(d, len(frames), len(frames[0]), sb, 6) for g in f]
+    bad = [i for i, (g, s) in enumerate(zip(got, strips)) if bytes(g) != zlib.compress(s, 6)]
+    print(what, "strips", len(strips), "lazy", n_lazy, "per_round", per, "rounds", rounds, "bad", bad[:20])
+    if bad:
+        print(describe_mismatch(got[bad[0]], zlib.compress(strips[bad[0]], 6)))
+    assert rounds > 1 and len(got) == len(strips) and not bad
+    assert 0 < n_lazy < len(strips)
+print("all rounds ok")
+'''
+
+
+@pytest.mark.parametrize("per_round", [6, 1])
+def test_rounds_with_both_kinds(per_round):
+    """The 64 KiB corpus call and the 5 000-byte call in rounds of 6 strips and of
+    one strip (VCF_ZX_BUDGET, read once per process: a child process): K1's list
+    is reset every round and the side kernels read the list of this round's slots."""
+    import os
+    import subprocess
+    import sys
+    from vcf_amd.zlib_gpu import workspace
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    budget = per_round * workspace(1) + (4096 if per_round > 1 else 0)
+    env = dict(os.environ, VCF_ZX_BUDGET=str(budget))
+    p = subprocess.run([sys.executable, "-c", _ROUNDS, root, os.path.join(root, "tests")], env=env,
+                       capture_output=True, text=True, timeout=120)
+    print(p.stdout[-3000:])
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
+    assert "all rounds ok" in p.stdout and f"per_round {per_round} " in p.stdout
+
+
+@pytest.mark.parametrize("strip", [4099, 65521])
+@pytest.mark.parametrize("offset", [1, 2, 3])
+def test_unaligned_source(offset, strip):
+    """Frames from an odd byte offset, odd strip lengths: over two frames of three
+    strips the strip starts take every residue mod 4 (K1's dword staging, K2's
+    window fill, the lazy parse's window fill and far compares); lazy
+    (sparse_rows_7873) and non-lazy (skewed) content."""
+    from deflate_cases import corpus
+    c = corpus()
+    frames = [np.resize(np.frombuffer(c[name], np.uint8), 3 * strip).tobytes()
+              for name in ("sparse_rows_7873", "skewed")]
+    names = ["sparse_rows_7873", "skewed"]
+    for level in (6, 9):
+        res = _deflate(frames, strip, level, offset=offset)
+        assert len(res) == 6
+        _assert_zlib(res, level, lambda fk: f"{names[fk[0]]} strip {fk[1]} offset {offset}")
+    n_lazy, n_non = _assert_parse_info([s for _, s, _ in res], [f"{names[i // 3]} {i % 3}" for i in range(6)])
+    assert n_lazy == 3 and n_non == 3
+
+
+def test_corpus_three_runs_identical():
+    """The level-6 corpus call three times in one process with another deflate (the
+    long-list call) in between: the same bytes every time, whatever the other
+    call's workgroups left in LDS and in the workspace."""
+    from deflate_cases import STRIP, small_strip_frame
+    runs = []
+    for r in range(3):
+        entries, res = _corpus_call(STRIP, 6)
+        runs.append([g for _, _, g in res])
+        if r == 0:
+            _assert_zlib(res, 6, lambda fk: entries[fk[0]][0])
+        if r < 2:
+            _deflate([small_strip_frame(272, 4500, 320, 1)], 272, 6)
+    for r in (1, 2):
+        diff = [entries[i][0] for i in range(len(entries)) if runs[r][i] != runs[0][i]]
+        assert not diff, (r, diff)

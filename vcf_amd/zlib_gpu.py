@@ -156,6 +156,34 @@ class StripDeflater:
             blob = host.tobytes()
             return [[blob[offs[f * spf + k]:offs[f * spf + k + 1]] for k in range(spf)] for f in range(int(n_frames))]
 
+    def parse_info(self) -> dict:
+        """What K1 decided for every strip of the last call, read back from the
+        workspace; test use only (tests/test_deflate_gpu.py pins the host
+        restatement of K1's rule to it).  -> {"lazy": bool per strip (the parse
+        order word), "distinct": K1's distinct-hash count per strip, "listed":
+        the length of K1's list of non-lazy strips}.  Only a call of one round
+        leaves every strip's words in the workspace: ValueError otherwise."""
+        with self._lock:
+            total = getattr(self, "total", 0)
+            per = workspace(1)                      # one strip's workspace; its last 48 bytes are the words
+            if total == 0 or workspace(total) != total * per:
+                raise ValueError(f"parse_info: the last call ({total} strips) was not a single round")
+            ws = self._bufs["ws"]
+            table = np.empty((total, 3), np.int64)
+            table[:, 0] = np.arange(total, dtype=np.int64) * per + (per - 48)
+            table[:, 1] = np.arange(total, dtype=np.int64) * 48
+            table[:, 2] = 48
+            if int(table[-1, 0]) + 48 > ws.nbytes:
+                raise ValueError("parse_info: the workspace is smaller than the last call's strips")
+            tb = self._buf("info_table", table.nbytes)
+            tb.upload(table, self.stream)
+            dst = self._buf("info", total * 48)
+            copy_pieces(ws, tb, total, dst, self.stream)
+            words = np.empty((total, 12), np.uint32)
+            dst.download(words, self.stream)
+            self.stream.synchronize()
+            return {"lazy": words[:, 5] != 0, "distinct": words[:, 6].copy(), "listed": int(words[0, 10])}
+
     def close(self):
         for b in self._bufs.values():
             b.free()
