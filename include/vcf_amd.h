@@ -117,6 +117,36 @@ int vcf_dct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t
                       int32_t block_size, int32_t Q, uint32_t flags, uint8_t *rgb_dev,
                       void *stream);
 
+/* ---- lapped 2D-MDCT + deadzone path (2D-MDCT.py) ---------------------------- */
+
+/* Padded shape and the pads stored in {out}_shape.bin (2D-MDCT.py:446-476):
+ * Hp = ceil((H + 2B) / B) * B (one extra block of context per side), pad_top =
+ * (Hp - H) / 2, likewise for the width.  Host only.  2 <= block_size <= 64,
+ * else VCF_ERR_UNSUPPORTED. */
+int vcf_mdct_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp, int32_t *Wp, int32_t *pad_top,
+                          int32_t *pad_left);
+
+/* 2D-MDCT.py encode_fn :498-582 between the image read and the entropy codec:
+ * n_frames RGB frames (H x W x 3 u8) -> coefficient frames (Hp x Wp x 3 u8 of
+ * vcf_mdct_padded_shape): centred symmetric pad, -128, YCoCg, Malvar's lapped
+ * transform (rows, then columns, float64), / scale, deadzone with step Q,
+ * +128, CLIPPED to [0, 255] (not the DCT path's wrap); subband layout unless
+ * VCF_DCT_NO_SUBBANDS.  Every 2 <= block_size <= 64 (else VCF_ERR_UNSUPPORTED),
+ * H, W >= 1 (frames smaller than a block are legal), 1 <= Q <= 32767.
+ * VCF_DCT_PERCEPTUAL is taken at block_size 8 only, where the reference's
+ * cv2.resize of the JPEG tables is the identity; at other sizes it returns
+ * VCF_ERR_UNSUPPORTED: cv2 is not available to pin the resized tables.
+ * Argument errors are reported before any device work. */
+int vcf_mdct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
+                       int32_t Q, uint32_t flags, uint8_t *k_dev, void *stream);
+
+/* The inverse, 2D-MDCT.py decode_fn :587-666: coefficient frames -> RGB frames
+ * with the padding removed (int16 dequantizer, synthesis columns first, then
+ * rows, no boundary extension, * scale, RGB in float32, +128, clip, truncate).
+ * Same argument rules as vcf_mdct_dz_encode. */
+int vcf_mdct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
+                       int32_t Q, uint32_t flags, uint8_t *rgb_dev, void *stream);
+
 /* 1 if block_size has a HIP transform: every 1 <= B <= 4096 -- compiled
  * kernels for the 38 5-smooth B <= 128 (every -L candidate 2, 4, ..., 128,
  * 2D-DCT.py:536), run-time-length kernels for the rest: rfftp plans with the

@@ -38,7 +38,10 @@ def transform_codec(args):
     if name == "2D-DWT":
         from .dwt2d import CoDec
         return CoDec(args)
-    raise NotImplementedError(f"transform {name!r}: 2D-DCT and 2D-DWT are on the HIP path")
+    if name == "2D-MDCT":
+        from .mdct2d import CoDec
+        return CoDec(args)
+    raise NotImplementedError(f"transform {name!r}: 2D-DCT, 2D-DWT and 2D-MDCT are on the HIP path")
 
 
 def _frame_inputs(original: str, n: int):

@@ -176,6 +176,20 @@ def add_dct(enc, dec):
                        default=False)
 
 
+def add_mdct(enc, dec):
+    """2D-MDCT.py:54-78."""
+    for p, what in ((enc, "quantization"), (dec, "dequantization")):
+        p.add_argument("-B", "--block_size_MDCT", type=int_or_str,
+                       help=f"Block size (default: {DEFAULT_BLOCK_SIZE})", default=DEFAULT_BLOCK_SIZE)
+        p.add_argument("-t", "--color_transform", type=int_or_str,
+                       help=f"Color transform (default: \"{DEFAULT_CT}\")", default=DEFAULT_CT)
+        p.add_argument("-p", "--perceptual_quantization", action="store_true",
+                       help=f"Use perceptual {what} (default: \"False\")", default=False)
+        p.add_argument("-x", "--disable_subbands", action="store_true",
+                       help="Disable the coefficients reordering in subbands (default: \"False\")",
+                       default=False)
+
+
 def add_dwt(enc, dec):
     """2D-DWT.py:25-31."""
     for p in (enc, dec):
@@ -209,6 +223,18 @@ def dct_parser(description: str = "Exploiting spatial redundancy with the 2D Dis
     return p
 
 
+def mdct_parser(description: str = "Exploiting spatial redundancy with the Modified Discrete Cosine "
+                                   "Transform (MDCT).", entropy: str = DEFAULT_EIC):
+    """`python 2D-MDCT.py ...` (2D-MDCT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py)."""
+    p, enc, dec = base_parser(description)
+    add_mdct(enc, dec)
+    add_ycocg(enc, dec)
+    add_deadzone(enc, dec)
+    add_filter(enc, dec, entropy)
+    add_eic(enc, dec)
+    return p
+
+
 def dwt_parser(description: str = "Exploiting spatial redundancy with the 2D dyadic Discrete Wavelet "
                                   "Transform.", entropy: str = DEFAULT_EIC):
     """`python 2D-DWT.py ...` (2D-DWT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py)."""
@@ -228,6 +254,8 @@ def iii_parser(description: str = "III coding: runs a 2D image codec for each im
     add_iii(enc, dec)
     if transform == "2D-DWT":
         add_dwt(enc, dec)
+    elif transform == "2D-MDCT":
+        add_mdct(enc, dec)
     else:
         add_dct(enc, dec)
     add_ycocg(enc, dec)
