@@ -225,12 +225,7 @@ def test_dct_decode_any_block_size_on_any_indices(B):
 
 def _unfused(DW, *a):
     """DW.decode with the inverse levels 2 + 1 as two line-kernel launches."""
-    from vcf_amd import _lib as L
-    L.call("vcf_dwt_set_inverse_band21", 0)
-    try:
-        return DW.decode(*a)
-    finally:
-        L.call("vcf_dwt_set_inverse_band21", 1)
+    return DW.decode(*a, schedule={"band21": 0})
 
 
 @pytest.mark.parametrize("wavelet", ["bior4.4", "db5"])

@@ -301,12 +301,7 @@ def test_dwt_line_decode_4k(wavelet):
 
 def _decode_unfused(DW, *a):
     """DW.decode with the inverse levels 2 + 1 as two line-kernel launches."""
-    from vcf_amd import _lib as Lb
-    Lb.call("vcf_dwt_set_inverse_band21", 0)
-    try:
-        return DW.decode(*a)
-    finally:
-        Lb.call("vcf_dwt_set_inverse_band21", 1)
+    return DW.decode(*a, schedule={"band21": 0})
 
 
 @pytest.mark.parametrize("wavelet,H,W,L,Q", [
@@ -332,3 +327,82 @@ def test_dwt_decode_band21_equals_two_launches(wavelet, H, W, L, Q):
     assert np.array_equal(fused, two)
     f = 1 if H * W > 1e6 else 0
     assert np.array_equal(fused[f], O.dwt_decode_frame(sb[f], H, W, wavelet, L, Q))
+
+
+# ---- forced kernel schedules (the A/B library's vcf_dwt_dz_*_sched: the product's launch code under a
+# caller's vcf_dwt_schedule) give the default schedule's bytes
+
+def _noise(n, H, W, seed):
+    return np.random.Generator(np.random.PCG64(seed)).integers(0, 256, (n, H, W, 3), dtype=np.uint8)
+
+
+def _same_subbands(got, ref, what):
+    for f in range(len(ref)):
+        for name in ref[f]:
+            assert np.array_equal(got[f][name], ref[f][name]), (what, f, name)
+
+
+@pytest.mark.parametrize("wavelet", ["bior4.4", "db5"])
+@pytest.mark.parametrize("L", [2, 3])
+def test_dwt_schedule_enc_bands(wavelet, L):
+    """The level 1 + 2 kernel on the smallest plane band12_ok accepts (64 x 512: h2 = 16, at most 8 bands;
+    LL2 the final u16 with L = 2, float64 for level 3 with L = 3) under every band cut."""
+    import vcf_amd.dwt as DW
+    H, W, Q = 64, 512, 32
+    frames = _noise(2, H, W, 41 + L)
+    ref = DW.encode(frames, wavelet, L, Q)
+    _same_subbands(DW.encode(frames, wavelet, L, Q, variant=27), ref, "variant 27")
+    for bands in (1, 2, 3, 8):
+        _same_subbands(DW.encode(frames, wavelet, L, Q, schedule={"enc_bands": bands}), ref, bands)
+
+
+@pytest.mark.parametrize("wavelet", ["bior4.4", "db5"])
+@pytest.mark.parametrize("H,W", [(96, 136),    # level 3 on the line kernel: 12 output row pairs
+                                 (90, 140)])   # h1 = 45 odd: every level on the line kernel
+def test_dwt_schedule_dec_line_bands(wavelet, H, W):
+    import vcf_amd.dwt as DW
+    L, Q = 3, 32
+    sb = DW.encode(_noise(3, H, W, H + W), wavelet, L, Q)
+    ref = DW.decode(sb, H, W, wavelet, L, Q)
+    assert np.array_equal(DW.decode(sb, H, W, wavelet, L, Q, variant=17), ref)
+    for bands in (1, 2, 5, 12):
+        assert np.array_equal(DW.decode(sb, H, W, wavelet, L, Q, schedule={"dec_line_bands": bands}), ref), bands
+
+
+@pytest.mark.parametrize("wavelet", ["bior4.4", "db5"])
+@pytest.mark.parametrize("H,W,L,Q", [(96, 136, 2, 32), (120, 248, 3, 7)])
+def test_dwt_schedule_dec21_brows(wavelet, H, W, L, Q):
+    """The inverse levels 2 + 1 kernel in bands of 2, 16, 22 (a partial last band) and h1 level-1 rows."""
+    import vcf_amd.dwt as DW
+    sb = DW.encode(_noise(3, H, W, H + W), wavelet, L, Q)
+    ref = DW.decode(sb, H, W, wavelet, L, Q)
+    assert np.array_equal(DW.decode(sb, H, W, wavelet, L, Q, variant=17), ref)
+    for brows in (2, 16, 22, (H + 1) // 2):
+        assert np.array_equal(DW.decode(sb, H, W, wavelet, L, Q, schedule={"dec21_brows": brows}), ref), brows
+
+
+@pytest.mark.parametrize("wavelet", ["bior4.4", "db5"])
+def test_dwt_schedule_pipelines(wavelet):
+    """Two frames of 2^20 pixels (pipeline_default's threshold) as two chunks on the library's streams,
+    the chunks keeping the call's band cut: the encode, then the decode."""
+    import vcf_amd.dwt as DW
+    H, W, L, Q = 1024, 1024, 3, 32
+    frames = _noise(2, H, W, 77)
+    ref = DW.encode(frames, wavelet, L, Q)
+    _same_subbands(DW.encode(frames, wavelet, L, Q, variant=27), ref, "variant 27")
+    _same_subbands(DW.encode(frames, wavelet, L, Q, schedule={"enc_pipe": 1}), ref, "enc_pipe")
+    dref = DW.decode(ref, H, W, wavelet, L, Q)
+    assert np.array_equal(DW.decode(ref, H, W, wavelet, L, Q, variant=17), dref)
+    assert np.array_equal(DW.decode(ref, H, W, wavelet, L, Q, schedule={"dec_pipe": 1}), dref)
+
+
+def test_dwt_schedule_unknown_field():
+    import vcf_amd.dwt as DW
+    frame = np.zeros((16, 16, 3), np.uint8)
+    with pytest.raises(ValueError, match="enc_band"):
+        DW.encode(frame, "db5", 2, 32, schedule={"enc_band": 2})
+    sb = DW.encode(frame, "db5", 2, 32)
+    with pytest.raises(ValueError, match="bands"):
+        DW.decode(sb, 16, 16, "db5", 2, 32, schedule={"bands": 1, "band21": 0})
+    with pytest.raises(ValueError):
+        DW.encode(frame, "db5", 2, 32, variant=1, schedule={"enc_bands": 2})

@@ -117,14 +117,9 @@ def test_lift_rejects_other_wavelets():
         DW.encode(np.zeros((32, 32, 3), np.uint8), "db5", 2, 32, lifting=True)
 
 
-def _unfused(fn):
-    """fn() with the lifting path's level pairs unfused (one launch per level)."""
-    from vcf_amd import _lib as Lb
-    Lb.call("vcf_dwt_lift_set_fused", 0)
-    try:
-        return fn()
-    finally:
-        Lb.call("vcf_dwt_lift_set_fused", 1)
+def _unfused(fn, *a):
+    """fn (DW.encode / DW.decode) on the lifting path with its level pairs unfused (one launch per level)."""
+    return fn(*a, lifting=True, schedule={"lift_fused": 0})
 
 
 @pytest.mark.parametrize("H,W,L,Q", [(96, 240, 2, 32), (64, 480, 5, 32), (32, 176, 3, 7), (200, 496, 2, 300),
@@ -140,7 +135,7 @@ def test_lift_fused_levels12_equal_unfused(monkeypatch, H, W, L, Q):
     frames = (np.stack([bench.synth_frame(H, W, 5), rng.integers(0, 256, (H, W, 3), dtype=np.uint8)])
               if H * W < 4e6 else bench.synth_frame(H, W, 5)[None])
     fused = DW.encode(frames, "bior4.4", L, Q, lifting=True)
-    split = _unfused(lambda: DW.encode(frames, "bior4.4", L, Q, lifting=True))
+    split = _unfused(DW.encode, frames, "bior4.4", L, Q)
     for f in range(len(frames)):
         for name in fused[f]:
             assert np.array_equal(fused[f][name], split[f][name]), (f, name)
@@ -161,7 +156,7 @@ def test_lift_fused_levels21_decode_equal_unfused(monkeypatch, H, W, L, Q):
               if H * W < 4e6 else bench.synth_frame(H, W, 6)[None])
     sb = DW.encode(frames, "bior4.4", L, Q)
     fused = DW.decode(sb, H, W, "bior4.4", L, Q, lifting=True)
-    split = _unfused(lambda: DW.decode(sb, H, W, "bior4.4", L, Q, lifting=True))
+    split = _unfused(DW.decode, sb, H, W, "bior4.4", L, Q)
     assert np.array_equal(fused, split)
     if H * W < 4e6:
         want = O.dwt_decode_frame(sb[0], H, W, "bior4.4", L, Q)

@@ -140,8 +140,6 @@ SIGNATURES = {
     "vcf_zlib_bound": [_I64],
     "vcf_zlib_workspace": [_I64],
     "vcf_zlib_set_workspace_budget": [_I64],
-    "vcf_dwt_lift_set_fused": [_I32],
-    "vcf_dwt_set_inverse_band21": [_I32],
     "vcf_dwt_lift_analyze_f64": [_P, _I32, _I32, _I32, _P, _P, _P, _P],
     "vcf_zlib_max_strip": [],
     "vcf_inflate_strips": [_P, _P, _P, _I64, _P, _P, _P, _P, _P],
@@ -181,6 +179,23 @@ SIGNATURES = {
     "vcf_comm_gatherv": [_P, _P, _I64, _P, _P, ctypes.c_int, _P],
 }
 
+class DwtSchedule(ctypes.Structure):
+    """vcf_dwt_schedule (include/vcf_amd_ab.h): the kernel schedule of one 2D-DWT
+    call of the A/B library; the defaults are the library's rules."""
+    _fields_ = [(n, _I32) for n in ("enc_bands", "dec_line_bands", "dec21_brows", "enc_pipe", "dec_pipe", "band21",
+                                    "lift_fused")]
+    DEFAULTS = dict(enc_bands=0, dec_line_bands=0, dec21_brows=0, enc_pipe=-1, dec_pipe=-1, band21=1, lift_fused=1)
+
+    def __init__(self, **fields):
+        unknown = sorted(set(fields) - set(self.DEFAULTS))
+        if unknown:
+            raise ValueError(f"unknown DWT schedule field(s) {unknown}: one of {sorted(self.DEFAULTS)}")
+        super().__init__(**{**self.DEFAULTS, **{k: int(v) for k, v in fields.items()}})
+
+
+_PSCHED = ctypes.POINTER(DwtSchedule)
+_DWT_ARGS = [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]
+
 # the experimental A/B library (include/vcf_amd_ab.h): kernel variants, loaded
 # only by the A/B scripts and the cross-check tests
 AB_SIGNATURES = {
@@ -188,6 +203,10 @@ AB_SIGNATURES = {
     "vcf_dct_dz_decode_variant": [ctypes.c_int, _P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P],
     "vcf_dwt_dz_encode_variant": [_I32, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
     "vcf_dwt_dz_decode_variant": [_I32, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
+    "vcf_dwt_dz_encode_sched": [_PSCHED] + _DWT_ARGS,
+    "vcf_dwt_dz_decode_sched": [_PSCHED] + _DWT_ARGS,
+    "vcf_dwt_dz_encode_lift_sched": [_PSCHED] + _DWT_ARGS,
+    "vcf_dwt_dz_decode_lift_sched": [_PSCHED] + _DWT_ARGS,
     "vcf_inflate_strips_wincheck": [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P],
 }
 

@@ -26,16 +26,17 @@
 // rows then columns per level and a final YCoCg->RGB kernel.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 
 #include "vcf_amd.h"
+#include "vcf_band_cut.h"
 #include "vcf_internal.h"
 #include "vcf_pipeline.h"
 #include "vcf_wavelets.h"
@@ -1289,6 +1290,69 @@ int check_dwt(const void *a, const void *b, int64_t n_frames, int32_t H, int32_t
 
 unsigned gx(int n) { return (unsigned)((n + 255) / 256); }
 
+// The kernel schedule of one call; the defaults are the library's rules.  The
+// product entry points pass DwtSchedule{}; the A/B library's vcf_dwt_dz_*_sched
+// (ab/vcf_dwt_sched.hip, include/vcf_amd_ab.h) pass a caller's.  Every setting
+// gives the same bytes.
+struct DwtSchedule {
+    int enc_bands = 0;        // bands of the level 1 + 2 kernel (0 = the cost model)
+    int dec_line_bands = 0;   // bands of each inverse line launch (0 = the cost model)
+    int dec21_brows = 0;      // level-1 rows per band of the inverse levels 2 + 1 kernel (0 = its rule)
+    int enc_pipe = -1;        // the encode as a frame pipeline: -1 = the rule, 0 off, 1 on where pipeline_default
+    int dec_pipe = -1;        // the decode likewise (the rule: off)
+    int band21 = 1;           // inverse levels 2 and 1 in one launch where band21_ok
+    int lift_fused = 1;       // the lifting form's level pairs in one launch
+};
+
+// resident workgroups of one kernel on the current device: its CUs x the
+// `threads`-wide workgroups of kern that fit one (fallback_per_cu where the
+// query fails; kern == nullptr: fallback_per_cu is the count), cached per
+// (device, kernel)
+std::mutex g_slots_mu;
+std::map<std::pair<int, const void *>, int> g_slots;
+
+int resident_slots(const void *kern, int threads, int fallback_per_cu)
+{
+    int dev = 0, n_cu = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    std::lock_guard<std::mutex> lk(g_slots_mu);
+    int &slots = g_slots[{dev, kern}];
+    if (!slots) {
+        if (dev < 0 || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+            n_cu = 256;
+        if (!kern || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0) != hipSuccess || per_cu <= 0)
+            per_cu = fallback_per_cu;
+        slots = n_cu * per_cu;
+    }
+    return slots;
+}
+
+// the bit-exact path's float64 planes in a call's workspace (plane_doubles per
+// frame and channel): the column-pass pair A / D, then the LL ping-pong pair
+struct DwtPlanes {
+    double *A, *D, *P0, *P1;
+};
+
+DwtPlanes dwt_planes(const DwtGeom &g, void *workspace_dev)
+{
+    double *A = (double *)workspace_dev;
+    double *D = A + std::max<long long>((long long)g.hs[1] * g.ws[0], (long long)g.hs[1] * 2 * g.ws[1]);
+    double *P0 = D + (D - A);
+    return {A, D, P0, P0 + 4LL * g.hs[1] * g.ws[1]};
+}
+
+// the lifting path's ping-pong pair (the second plane starts 16-byte aligned:
+// the kernels' double2 loads)
+struct LiftPlanes {
+    double *P[2];
+};
+
+LiftPlanes lift_planes(const DwtGeom &g, void *workspace_dev)
+{
+    double *p = (double *)workspace_dev;
+    return {{p, p + ((long long)g.hs[1] * g.ws[1] + 1) / 2 * 2}};
+}
+
 bool fast_filter(int F) { return F >= 2 && F <= kMaxFastF && (F & 1) == 0; }
 
 template <int F>
@@ -1474,37 +1538,17 @@ bool band12_ok(const DwtGeom &g, const WaveletDef &wd, int &id)
 
 template <unsigned ZL, unsigned ZH, int CT>
 void launch_band12_t(const DwtGeom &g, const uint8_t *rgb, long long n_frames, double *LL2, long long plane_stride,
-                     uint8_t *packed, int Q, hipStream_t s, long long rule_frames)
+                     uint8_t *packed, int Q, hipStream_t s, long long rule_frames, const DwtSchedule &sc)
 {
     const int h2 = g.hs[2], w2 = g.ws[2];
     const int n_tiles = (w2 + kBT2 - 1) / kBT2;
-    // bands: the time is about (rounds of resident workgroups) x (steps per band,
-    // 2 rows + the F - 2 halo rows + 3 of pipeline per level-2 row pair); two
-    // 512-thread workgroups fit a CU (VGPRs)
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0, v = 0;
-        n_cu = hipGetDevice(&dev) == hipSuccess &&
-                       hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0
-                   ? v
-                   : 256;
-    }
+    // bands (band_cut): per band 2 steps per level-2 row + the F - 2 halo rows + 3
+    // of pipeline per level-2 row pair; two 512-thread workgroups fit a CU (VGPRs)
     // (rule_frames: the frames of the whole call -- a pipelined call's chunks run side by side)
-    const long long slots = 2LL * n_cu, per_band = 3LL * rule_frames * n_tiles;
-    int n_bands = 1;
-    long long best = -1;
-    for (int nb = 1; nb <= std::max(1, h2 / 2); ++nb) {
-        const int br = (h2 + nb - 1) / nb;
-        if (nb > 1 && (h2 + br - 1) / br != nb) continue;
-        const long long rounds = (per_band * nb + slots - 1) / slots;
-        const long long cost = rounds * (2LL * br + 10 + 3);
-        if (best < 0 || cost < best) {
-            best = cost;
-            n_bands = nb;
-        }
-    }
-    if (const char *e = getenv("VCF_DWT_BANDS"))   // tuning knob (A/B of the band cut)
-        n_bands = std::max(1, std::min(atoi(e), std::max(1, h2 / 2)));
+    const long long slots = resident_slots(nullptr, kBNT, 2), per_band = 3LL * rule_frames * n_tiles;
+    const int max_bands = std::max(1, h2 / 2);
+    int n_bands = sc.enc_bands ? std::max(1, std::min(sc.enc_bands, max_bands))
+                               : band_cut(h2, max_bands, per_band, slots, 2, 10 + 3);
     const int brows = (h2 + n_bands - 1) / n_bands;
     n_bands = (h2 + brows - 1) / brows;
     const long long units = n_frames * n_tiles * n_bands;
@@ -1520,10 +1564,11 @@ void launch_band12_t(const DwtGeom &g, const uint8_t *rgb, long long n_frames, d
 }
 
 void launch_band12(int id, const DwtGeom &g, const uint8_t *rgb, long long n_frames, double *LL2,
-                   long long plane_stride, uint8_t *packed, int Q, hipStream_t s, long long rule_frames)
+                   long long plane_stride, uint8_t *packed, int Q, hipStream_t s, long long rule_frames,
+                   const DwtSchedule &sc)
 {
-    if (id == 1) launch_band12_t<kB44DecLo, kB44DecHi, 1>(g, rgb, n_frames, LL2, plane_stride, packed, Q, s, rule_frames);
-    else launch_band12_t<0u, 0u, 2>(g, rgb, n_frames, LL2, plane_stride, packed, Q, s, rule_frames);
+    if (id == 1) launch_band12_t<kB44DecLo, kB44DecHi, 1>(g, rgb, n_frames, LL2, plane_stride, packed, Q, s, rule_frames, sc);
+    else launch_band12_t<0u, 0u, 2>(g, rgb, n_frames, LL2, plane_stride, packed, Q, s, rule_frames, sc);
 }
 
 // Line-based inverse level (idwt_line_kernel): 10-tap reconstruction filters
@@ -1541,37 +1586,16 @@ bool line_ok(const WaveletDef &wd, int h, int w, int &id)
 }
 
 template <bool FP, bool RGB, unsigned ZL, unsigned ZH, int CT>
-void launch_line_t(const LevelArgs &a, uint8_t *rgb_out)
+void launch_line_t(const LevelArgs &a, uint8_t *rgb_out, const DwtSchedule &sc)
 {
     // Q <= 256: the detail dequant never wraps in int16 (the fma form)
     auto kern = a.Q <= 256 ? idwt_line_kernel<FP, RGB, ZL, ZH, CT, true> : idwt_line_kernel<FP, RGB, ZL, ZH, CT, false>;
-    static int slots = 0;   // resident workgroups on the device (per instantiation)
-    if (!slots) {
-        int dev = 0, n_cu = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-            n_cu = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kINT, 0) != hipSuccess || per_cu <= 0)
-            per_cu = 2;
-        slots = n_cu * per_cu;
-    }
+    const int slots = resident_slots((const void *)kern, kINT, 2);
     const int n_tiles = (a.w + kILC - 1) / kILC, ohp = (a.hh + 1) / 2;
-    // bands: time ~ (rounds of resident workgroups) x (steps per band: rows + 4 halo + 1)
+    // bands (band_cut): per band its output row pairs + 4 halo + 1
     const long long per_band = (long long)n_tiles * a.n_frames;
-    int n_bands = 1;
-    long long best = -1;
-    for (int nb = 1; nb <= ohp; ++nb) {
-        const int br = (ohp + nb - 1) / nb;
-        if (nb > 1 && (ohp + br - 1) / br != nb) continue;
-        const long long rounds = (per_band * nb + slots - 1) / slots;
-        const long long cost = rounds * (br + 5);
-        if (best < 0 || cost < best) {
-            best = cost;
-            n_bands = nb;
-        }
-    }
-    if (const char *e = getenv("VCF_IDWT_BANDS"))   // tuning knob (A/B of the band cut)
-        n_bands = std::max(1, std::min(atoi(e), ohp));
+    int n_bands = sc.dec_line_bands ? std::max(1, std::min(sc.dec_line_bands, ohp))
+                                    : band_cut(ohp, ohp, per_band, slots, 1, 4 + 1);
     const int brows = (ohp + n_bands - 1) / n_bands;
     n_bands = (ohp + brows - 1) / brows;
     const long long grid = per_band * n_bands;
@@ -1581,53 +1605,44 @@ void launch_line_t(const LevelArgs &a, uint8_t *rgb_out)
 }
 
 template <unsigned ZL, unsigned ZH, int CT>
-void launch_line_id(const LevelArgs &a, bool from_packed, bool to_rgb, uint8_t *rgb_out)
+void launch_line_id(const LevelArgs &a, bool from_packed, bool to_rgb, uint8_t *rgb_out, const DwtSchedule &sc)
 {
     if (from_packed) {
-        if (to_rgb) launch_line_t<true, true, ZL, ZH, CT>(a, rgb_out);
-        else launch_line_t<true, false, ZL, ZH, CT>(a, rgb_out);
+        if (to_rgb) launch_line_t<true, true, ZL, ZH, CT>(a, rgb_out, sc);
+        else launch_line_t<true, false, ZL, ZH, CT>(a, rgb_out, sc);
     } else {
-        if (to_rgb) launch_line_t<false, true, ZL, ZH, CT>(a, rgb_out);
-        else launch_line_t<false, false, ZL, ZH, CT>(a, rgb_out);
+        if (to_rgb) launch_line_t<false, true, ZL, ZH, CT>(a, rgb_out, sc);
+        else launch_line_t<false, false, ZL, ZH, CT>(a, rgb_out, sc);
     }
 }
 
-void launch_line(int id, const LevelArgs &a, bool from_packed, bool to_rgb, uint8_t *rgb_out)
+void launch_line(int id, const LevelArgs &a, bool from_packed, bool to_rgb, uint8_t *rgb_out, const DwtSchedule &sc)
 {
-    if (id == 1) launch_line_id<kB44RecLo, kB44RecHi, 1>(a, from_packed, to_rgb, rgb_out);
-    else launch_line_id<0u, 0u, 2>(a, from_packed, to_rgb, rgb_out);
+    if (id == 1) launch_line_id<kB44RecLo, kB44RecHi, 1>(a, from_packed, to_rgb, rgb_out, sc);
+    else launch_line_id<0u, 0u, 2>(a, from_packed, to_rgb, rgb_out, sc);
 }
 
 // Inverse levels 2 + 1 in one launch (idwt_band21_kernel): line_ok filters on
 // planes that halve evenly from level 2 to level 1 (h1 = 2 h2, w1 = 2 w2).
-std::atomic<int> g_band21{1};   // vcf_dwt_set_inverse_band21 (A/B and tests)
 bool band21_ok(const DwtGeom &g, const WaveletDef &wd, int &id)
 {
-    if (!g_band21.load(std::memory_order_relaxed) || g.levels < 2) return false;
+    if (g.levels < 2) return false;
     const int h2 = g.hs[2], w2 = g.ws[2], h1 = g.hs[1], w1 = g.ws[1];
     return h1 == 2 * h2 && w1 == 2 * w2 && line_ok(wd, h2, w2, id) && line_ok(wd, h1, w1, id);
 }
 
 template <bool FP, unsigned ZL, unsigned ZH, int CT>
 void launch_band21_t(const DwtGeom &g, const uint8_t *packed, long long n_frames, const double *prev,
-                     long long plane_stride, int lda, uint8_t *rgb, int Q, hipStream_t s, long long rule_frames)
+                     long long plane_stride, int lda, uint8_t *rgb, int Q, hipStream_t s, long long rule_frames,
+                     const DwtSchedule &sc)
 {
     auto kern = Q <= 256 ? idwt_band21_kernel<FP, ZL, ZH, CT, true> : idwt_band21_kernel<FP, ZL, ZH, CT, false>;
-    static int slots = 0;   // resident workgroups on the device (per instantiation)
-    if (!slots) {
-        int dev = 0, n_cu = 0, per_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-            n_cu = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kB21NT, 0) != hipSuccess || per_cu <= 0)
-            per_cu = 2;
-        slots = n_cu * per_cu;
-    }
+    const int slots = resident_slots((const void *)kern, kB21NT, 2);
     const int h1 = g.hs[1], w1 = g.ws[1];
     const int n_tiles = (w1 + kB21C - 1) / kB21C;
     // bands of an even number of level-1 rows: the shortest bands (each re-reads a 7-row
     // halo) that still leave at most three workgroups per resident slot -- measured
-    // (scripts/dwt_bands_scan.py, profiles/r06_dwt_band_cuts_decode.json): C3 decode 0.546 ms
+    // (scripts/dwt_sched_ab.py dec21_brows, profiles/r06_dwt_band_cuts_decode.json): C3 decode 0.546 ms
     // with one round of 216-row bands (the previous rounds x (rows + 7) model's pick), 0.529
     // with 60-108 rows, 0.655 with 360: a few rounds of shorter bands balance better
     // (rule_frames: the frames of the whole call -- a pipelined call's chunks run side by side)
@@ -1638,8 +1653,7 @@ void launch_band21_t(const DwtGeom &g, const uint8_t *packed, long long n_frames
             brows = br;
             break;
         }
-    if (const char *e = getenv("VCF_IDWT21_BROWS"))   // tuning knob (A/B of the band cut): level-1 rows per band
-        brows = std::max(2, std::min(atoi(e) / 2 * 2, (h1 + 1) / 2 * 2));
+    if (sc.dec21_brows) brows = std::max(2, std::min(sc.dec21_brows / 2 * 2, (h1 + 1) / 2 * 2));
     const int n_bands = (h1 + brows - 1) / brows;
     const long long grid = (long long)n_tiles * n_frames * n_bands;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kB21NT), 0, s, packed, g.packed_bytes, g.ll_off,
@@ -1648,16 +1662,17 @@ void launch_band21_t(const DwtGeom &g, const uint8_t *packed, long long n_frames
 }
 
 void launch_band21(int id, const DwtGeom &g, const uint8_t *packed, long long n_frames, const double *prev,
-                   long long plane_stride, int lda, uint8_t *rgb, int Q, hipStream_t s, long long rule_frames)
+                   long long plane_stride, int lda, uint8_t *rgb, int Q, hipStream_t s, long long rule_frames,
+                   const DwtSchedule &sc)
 {
     const bool fp = g.levels == 2;   // LL2 from the packed u16 subband, else the level-3 plane
     const long long rf = rule_frames;
     if (id == 1) {
-        if (fp) launch_band21_t<true, kB44RecLo, kB44RecHi, 1>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf);
-        else launch_band21_t<false, kB44RecLo, kB44RecHi, 1>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf);
+        if (fp) launch_band21_t<true, kB44RecLo, kB44RecHi, 1>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf, sc);
+        else launch_band21_t<false, kB44RecLo, kB44RecHi, 1>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf, sc);
     } else {
-        if (fp) launch_band21_t<true, 0u, 0u, 2>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf);
-        else launch_band21_t<false, 0u, 0u, 2>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf);
+        if (fp) launch_band21_t<true, 0u, 0u, 2>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf, sc);
+        else launch_band21_t<false, 0u, 0u, 2>(g, packed, n_frames, prev, plane_stride, lda, rgb, Q, s, rf, sc);
     }
 }
 
@@ -1727,35 +1742,13 @@ constexpr PipeShape kEncodePipe{2, 2, false};
 // ---------------------------------------------------------------------------
 // lifting path (vcf_dwt_lift.h): launches
 // ---------------------------------------------------------------------------
-// resident workgroups of one kernel on the device
+// band rows of a lifting launch (band_cut): per band its row pairs + the 4 of the
+// pipeline's warm-up (a fused level pair: 2 steps per upper-level row + 12)
 template <typename K>
-int resident_slots(K kern, int threads)
+int lift_brows(K kern, long long per_band, int rows, int steps_per_row = 1, int warmup = 4)
 {
-    int dev = 0, n_cu = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-        n_cu = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0) != hipSuccess || per_cu <= 0)
-        per_cu = 4;
-    return n_cu * per_cu;
-}
-
-// band rows of a lifting launch: time ~ (rounds of resident workgroups) x
-// (row pairs per band + the 4 of the pipeline's warm-up)
-int lift_brows(long long per_band, int rows, int slots, int steps_per_row = 1, int warmup = 4)
-{
-    int n_bands = 1;
-    long long best = -1;
-    for (int nb = 1; nb <= rows; ++nb) {
-        const int br = (rows + nb - 1) / nb;
-        if (nb > 1 && (rows + br - 1) / br != nb) continue;
-        const long long rounds = (per_band * nb + slots - 1) / slots;
-        const long long cost = rounds * ((long long)steps_per_row * br + warmup);
-        if (best < 0 || cost < best) {
-            best = cost;
-            n_bands = nb;
-        }
-    }
+    const int slots = resident_slots((const void *)kern, lift::kNT, 4);
+    const int n_bands = band_cut(rows, rows, per_band, slots, steps_per_row, warmup);
     return (rows + n_bands - 1) / n_bands;
 }
 
@@ -1767,11 +1760,6 @@ int lift_check(int wavelet)
 }
 
 #endif  // VCF_DWT_KERNELS_ONLY
-// A/B knob of the opt-in lifting path (tests/test_dwt_lift_gpu.py compares the two
-// forms): vcf_dwt_lift_set_fused(0) selects one launch per level instead of the
-// fused level pairs, for the whole process.
-std::atomic<int> g_lift_fused{1};
-inline bool lift_nofuse() { return g_lift_fused.load(std::memory_order_relaxed) == 0; }
 }  // namespace
 }  // namespace vcf
 
@@ -1780,6 +1768,7 @@ using namespace vcf;
 
 extern "C" {
 
+#ifndef VCF_DWT_SCHED_BUILD   // (the A/B library has these from ab/vcf_dwt_ab.hip)
 int vcf_wavelet_index(const char *name, int32_t *index)
 {
     if (!name || !index) return set_error(VCF_ERR_INVALID, "null pointer");
@@ -1805,6 +1794,7 @@ int vcf_dwt_layout(int32_t H, int32_t W, int32_t levels, int32_t *sub_h, int32_t
     if (workspace_bytes_per_frame) *workspace_bytes_per_frame = 3 * plane_doubles(g) * (int64_t)sizeof(double);
     return VCF_OK;
 }
+#endif
 
 // one stream's level chain of the encode (the frame pipeline calls it per
 // chunk of frames with its hook).  Levels: 1 and 2 in one band launch when
@@ -1818,7 +1808,7 @@ constexpr long long kSepArea = 40000;
 
 static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                         int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, hipStream_t s,
-                        const PipeHook *hook, long long rule_frames)
+                        const PipeHook *hook, long long rule_frames, const DwtSchedule &sc)
 {
     int rc = VCF_OK;
     Filters flt;
@@ -1826,11 +1816,9 @@ static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int
     DwtGeom g;
     dwt_geom(H, W, levels, kWavelets[wavelet].len, g);
     const int F = g.F;
-    const long long pd = plane_doubles(g);
-    double *base = (double *)workspace_dev;
-    const long long ws_stride = pd;                          // per plane
-    double *A = base, *D = base + std::max<long long>((long long)g.hs[1] * g.ws[0], (long long)g.hs[1] * 2 * g.ws[1]);
-    double *LL0 = D + (D - A), *LL1 = LL0 + 4LL * g.hs[1] * g.ws[1];
+    const long long ws_stride = plane_doubles(g);            // per plane
+    const DwtPlanes pl = dwt_planes(g, workspace_dev);
+    double *const A = pl.A, *const D = pl.D, *const LL0 = pl.P0, *const LL1 = pl.P1;
     const unsigned planes = (unsigned)(n_frames * 3);
     const double *in = nullptr;
     const bool fused = fast_filter(F);
@@ -1858,7 +1846,7 @@ static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int
     if (fused && band12_ok(g, kWavelets[wavelet], band_id)) {
         // levels 1 and 2 in one launch: LL1 never leaves the chip; LL2 lands where level 2's would
         if ((rc = hook_wait(hook, s)) != VCF_OK) return rc;
-        launch_band12(band_id, g, rgb_dev, n_frames, LL1, ws_stride, packed_dev, Q, s, rule_frames);
+        launch_band12(band_id, g, rgb_dev, n_frames, LL1, ws_stride, packed_dev, Q, s, rule_frames, sc);
         if ((rc = hip_check(hipGetLastError(), "dwt_band12_kernel launch")) != VCF_OK) return rc;
         if ((rc = hook_rec(hook, s)) != VCF_OK) return rc;
         in = LL1;
@@ -1885,8 +1873,8 @@ static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int
     return VCF_OK;
 }
 
-int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
-                      int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
+static int dwt_encode(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
+                      int32_t wavelet, int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
 {
     int rc = check_dwt(rgb_dev, packed_dev, n_frames, H, W, wavelet, levels, Q, false);
     if (rc != VCF_OK) return rc;
@@ -1901,17 +1889,16 @@ int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
     // level-1+2 band kernel one launch fills the chip (C3: 0.594 ms on one
     // stream vs 0.635 ms pipelined, ABBA)
     const bool band = fast_filter(g.F) && band12_ok(g, kWavelets[wavelet], id);
-    bool pipe = !band && fast_filter(g.F) && pipeline_default(n_frames, H, W);
-    // (A/B: VCF_DWT_ENC_PIPE=0/1, read per call; with the band kernel the chunks keep the call's band cut)
-    if (const char *e = getenv("VCF_DWT_ENC_PIPE")) pipe = atoi(e) != 0 && fast_filter(g.F) && pipeline_default(n_frames, H, W);
+    // (A/B: sc.enc_pipe 0 / 1; with the band kernel the chunks keep the call's band cut)
+    const bool pipe = (sc.enc_pipe < 0 ? !band : sc.enc_pipe != 0) && fast_filter(g.F) && pipeline_default(n_frames, H, W);
     if (pipe) {
         const long long fpx = (long long)H * W * 3, wsf = 3 * plane_doubles(g);
         return run_pipelined(n_frames, kEncodePipe, s, [&](long long f0, long long n, hipStream_t cs, const PipeHook *hook) {
             return encode_chain(rgb_dev + f0 * fpx, n, H, W, wavelet, levels, Q, packed_dev + f0 * g.packed_bytes,
-                                (double *)workspace_dev + f0 * wsf, cs, hook, n_frames);
+                                (double *)workspace_dev + f0 * wsf, cs, hook, n_frames, sc);
         });
     }
-    return encode_chain(rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev, s, nullptr, n_frames);
+    return encode_chain(rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev, s, nullptr, n_frames, sc);
 }
 
 // one stream's level chain of the decode: coarsest level first; the line
@@ -1923,7 +1910,7 @@ int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
 // calls it per chunk); rule_frames: the call's frames, for the band cut of levels 2 + 1
 static int decode_chain_fast(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                              int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, hipStream_t s,
-                             long long rule_frames)
+                             long long rule_frames, const DwtSchedule &sc)
 {
     int rc = VCF_OK;
     Filters flt;
@@ -1931,28 +1918,25 @@ static int decode_chain_fast(const uint8_t *packed_dev, int64_t n_frames, int32_
     DwtGeom g;
     dwt_geom(H, W, levels, kWavelets[wavelet].len, g);
     const int F = g.F;
-    const long long pd = plane_doubles(g);
-    double *base = (double *)workspace_dev;
-    const long long ws_stride = pd;
-    double *A = base, *D = base + std::max<long long>((long long)g.hs[1] * g.ws[0], (long long)g.hs[1] * 2 * g.ws[1]);
-    double *P0 = D + (D - A), *P1 = P0 + 4LL * g.hs[1] * g.ws[1];
+    const long long ws_stride = plane_doubles(g);
+    const DwtPlanes pl = dwt_planes(g, workspace_dev);
     const double *prev = nullptr;
     int lda = 0;
     int id21 = 0;
-    const bool b21 = band21_ok(g, kWavelets[wavelet], id21);
+    const bool b21 = sc.band21 && band21_ok(g, kWavelets[wavelet], id21);
     for (int r = levels; r >= 1; --r) {
         if (b21 && r == 2) {   // levels 2 and 1 in one launch, LL1 on chip
-            launch_band21(id21, g, packed_dev, n_frames, prev, ws_stride, lda, rgb_dev, Q, s, rule_frames);
+            launch_band21(id21, g, packed_dev, n_frames, prev, ws_stride, lda, rgb_dev, Q, s, rule_frames, sc);
             return hip_check(hipGetLastError(), "idwt_band21_kernel launch");
         }
         const int h = g.hs[r], w = g.ws[r];
         const int oh = r > 1 ? g.hs[r - 1] : 2 * h, ow = r > 1 ? g.ws[r - 1] : 2 * w;
-        double *out = (r & 1) ? P0 : P1;
+        double *out = (r & 1) ? pl.P0 : pl.P1;
         const LevelArgs a{nullptr, 0, prev, ws_stride, out, const_cast<uint8_t *>(packed_dev), g.packed_bytes,
                           g.ll_off, g.sb_off[r][0], g.sb_off[r][1], g.sb_off[r][2], h, w, oh, ow, Q, lda,
                           (unsigned)n_frames, flt, &kWavelets[wavelet], s};
         int id = 0;
-        if (line_ok(kWavelets[wavelet], h, w, id)) launch_line(id, a, r == levels, r == 1, rgb_dev);
+        if (line_ok(kWavelets[wavelet], h, w, id)) launch_line(id, a, r == levels, r == 1, rgb_dev, sc);
         else inv_level(F, a, r == levels, r == 1, rgb_dev);
         prev = out;
         lda = ow;
@@ -1965,14 +1949,11 @@ static int decode_chain_fast(const uint8_t *packed_dev, int64_t n_frames, int32_
 // coarse levels beside the other chunk's levels 2 + 1 band, the band cut kept at the
 // whole call's): off -- measured slower in every form, round 6's with the fused band
 // included (C3 0.591 vs 0.528 ms, profiles/r06_dwt_decode_pipeline_not_kept.json).
-// VCF_DWT_DEC_PIPE=1 (read per call) selects it for A/B.
+// sc.dec_pipe = 1 selects it for A/B.
 constexpr PipeShape kDecodePipe{2, 2, false};
-#ifndef VCF_DWT_DEC_PIPE_DEFAULT
-#define VCF_DWT_DEC_PIPE_DEFAULT 0
-#endif
 
-int vcf_dwt_dz_decode(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
-                      int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
+static int dwt_decode(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
+                      int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
 {
     int rc = check_dwt(packed_dev, rgb_dev, n_frames, H, W, wavelet, levels, Q, true);
     if (rc != VCF_OK) return rc;
@@ -1986,27 +1967,21 @@ int vcf_dwt_dz_decode(const uint8_t *packed_dev, int64_t n_frames, int32_t H, in
     dwt_geom(H, W, levels, kWavelets[wavelet].len, g);
     const int F = g.F;
     const long long pd = plane_doubles(g);
-    double *base = (double *)workspace_dev;
     const long long ws_stride = pd;
-    double *A = base, *D = base + std::max<long long>((long long)g.hs[1] * g.ws[0], (long long)g.hs[1] * 2 * g.ws[1]);
-    double *P0 = D + (D - A), *P1 = P0 + 4LL * g.hs[1] * g.ws[1];
+    const auto [A, D, P0, P1] = dwt_planes(g, workspace_dev);
     const unsigned planes = (unsigned)(n_frames * 3);
     const double *prev = nullptr;
     int lda = 0;
     const bool short_lines = g.hs[levels] < F / 2 || g.ws[levels] < F / 2;
     if (fast_filter(F) && !short_lines) {
-        int id21 = 0;
-        bool pipe = VCF_DWT_DEC_PIPE_DEFAULT && band21_ok(g, kWavelets[wavelet], id21) && levels > 2 &&
-                    pipeline_default(n_frames, H, W);
-        if (const char *e = getenv("VCF_DWT_DEC_PIPE")) pipe = atoi(e) != 0 && pipeline_default(n_frames, H, W);
-        if (pipe) {
+        if (sc.dec_pipe > 0 && pipeline_default(n_frames, H, W)) {
             const long long fpx = (long long)H * W * 3, wsf = 3 * pd;
             return run_pipelined(n_frames, kDecodePipe, s, [&](long long f0, long long n, hipStream_t cs, const PipeHook *) {
                 return decode_chain_fast(packed_dev + f0 * g.packed_bytes, n, H, W, wavelet, levels, Q,
-                                         rgb_dev + f0 * fpx, (double *)workspace_dev + f0 * wsf, cs, n_frames);
+                                         rgb_dev + f0 * fpx, (double *)workspace_dev + f0 * wsf, cs, n_frames, sc);
             });
         }
-        return decode_chain_fast(packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev, s, n_frames);
+        return decode_chain_fast(packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev, s, n_frames, sc);
     }
     for (int r = levels; r >= 1; --r) {
         const int h = g.hs[r], w = g.ws[r];
@@ -2034,20 +2009,9 @@ int vcf_dwt_dz_decode(const uint8_t *packed_dev, int64_t n_frames, int32_t H, in
 
 // The lifting path (vcf_dwt_lift.h): bior4.4 only, same buffers, layout and
 // workspace as vcf_dwt_dz_encode / _decode; results within +-1 of theirs.
-int vcf_dwt_set_inverse_band21(int32_t on)
-{
-    g_band21.store(on ? 1 : 0, std::memory_order_relaxed);
-    return VCF_OK;
-}
-
-int vcf_dwt_lift_set_fused(int32_t fused)
-{
-    g_lift_fused.store(fused ? 1 : 0, std::memory_order_relaxed);
-    return VCF_OK;
-}
-
-int vcf_dwt_dz_encode_lift(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
-                           int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
+static int dwt_encode_lift(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
+                           int32_t wavelet, int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev,
+                           void *stream)
 {
     int rc = check_dwt(rgb_dev, packed_dev, n_frames, H, W, wavelet, levels, Q, false);
     if (rc != VCF_OK || (rc = lift_check(wavelet)) != VCF_OK) return rc;
@@ -2057,17 +2021,16 @@ int vcf_dwt_dz_encode_lift(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, 
     DwtGeom g;
     dwt_geom(H, W, levels, 10, g);
     const long long pd = plane_doubles(g);
-    // (the second plane starts 16-byte aligned: the kernels' double2 loads)
-    double *P[2] = {(double *)workspace_dev, (double *)workspace_dev + ((long long)g.hs[1] * g.ws[1] + 1) / 2 * 2};
+    const LiftPlanes pl = lift_planes(g, workspace_dev);
     const bool qp2 = (Q & (Q - 1)) == 0;
     // explicit ping-pong: a launch reads `in` (level l - 1's LL) and writes the other plane
     const double *in = nullptr;
     int nb = 0;
-    const bool nofuse = lift_nofuse();
+    const bool nofuse = !sc.lift_fused;
     for (int l = 1; l <= levels;) {
         const int h = g.hs[l - 1], w = g.ws[l - 1], hh = g.hs[l], hw = g.ws[l];
         const bool first = l == 1;
-        double *out = P[nb];
+        double *out = pl.P[nb];
         // levels l and l + 1 in one launch (lift_fwd12_kernel) on planes that halve evenly
         // twice with dword-aligned level-l subband rows (C3: levels 1 + 2 and 3 + 4)
         if (!nofuse && l + 1 <= levels && w % 4 == 0 && h % 4 == 0 && hw % 8 == 0 && w == 2 * hw &&
@@ -2082,7 +2045,7 @@ int vcf_dwt_dz_encode_lift(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, 
             auto kern = first ? pick(std::true_type{}) : pick(std::false_type{});
             const int n_strips = (hw2 + lift::kV2 - 1) / lift::kV2;
             const long long per_band = n_frames * n_strips;
-            const int brows = lift_brows(per_band, hh2, resident_slots(kern, lift::kNT), 2, 12);
+            const int brows = lift_brows(kern, per_band, hh2, 2, 12);
             const int n_bands = (hh2 + brows - 1) / brows;
             const long long grid = per_band * n_bands;
             if (grid > 0x7fffffffLL) return set_error(VCF_ERR_INVALID, "too many frames per call");
@@ -2110,7 +2073,7 @@ int vcf_dwt_dz_encode_lift(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, 
                                          : lift::lift_fwd_kernel<true, false, false>)
                                  : (last ? lift::lift_fwd_kernel<false, true, false>
                                          : lift::lift_fwd_kernel<false, false, false>));
-        const int brows = lift_brows(per_band, hh, resident_slots(kern, lift::kNT));
+        const int brows = lift_brows(kern, per_band, hh);
         const int n_bands = (hh + brows - 1) / brows, n_edge = n_strips - n_int;
         const int brows_e = brows, n_bands_e = n_bands;
         const long long edge_blocks = n_frames * n_edge * n_bands_e;
@@ -2132,6 +2095,7 @@ int vcf_dwt_dz_encode_lift(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, 
 // level; coef_dev receives, per level l = 1..levels, the details [LH, HL, HH][Y, Co,
 // Cg][hs[l] x ws[l]], then LL_levels [Y, Co, Cg][hs x ws]; packed_dev (the packed
 // layout's bytes) receives Q = 1 indices as scratch.
+#ifndef VCF_DWT_SCHED_BUILD
 int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32_t levels, double *coef_dev,
                              uint8_t *packed_dev, void *workspace_dev, void *stream)
 {
@@ -2145,13 +2109,13 @@ int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32
     DwtGeom g;
     dwt_geom(H, W, levels, 10, g);
     const long long pd = plane_doubles(g);
-    double *P[2] = {(double *)workspace_dev, (double *)workspace_dev + ((long long)g.hs[1] * g.ws[1] + 1) / 2 * 2};
+    const LiftPlanes pl = lift_planes(g, workspace_dev);
     const double *in = nullptr;
     int nb = 0;
     double *raw = coef_dev;
     for (int l = 1; l <= levels; ++l) {
         const int h = g.hs[l - 1], w = g.ws[l - 1], hh = g.hs[l], hw = g.ws[l];
-        double *out = P[nb];
+        double *out = pl.P[nb];
         const int n_strips = (hw + lift::kValid - 1) / lift::kValid, brows = 16;
         const int n_bands = (hh + brows - 1) / brows;
         auto kern = l == 1 ? lift::lift_fwd_raw_kernel<true> : lift::lift_fwd_raw_kernel<false>;
@@ -2170,9 +2134,11 @@ int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32
             return rc;
     return VCF_OK;
 }
+#endif
 
-int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
-                           int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
+static int dwt_decode_lift(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
+                           int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev,
+                           void *stream)
 {
     int rc = check_dwt(packed_dev, rgb_dev, n_frames, H, W, wavelet, levels, Q, true);
     if (rc != VCF_OK || (rc = lift_check(wavelet)) != VCF_OK) return rc;
@@ -2182,15 +2148,15 @@ int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t 
     DwtGeom g;
     dwt_geom(H, W, levels, 10, g);
     const long long pd = plane_doubles(g);
-    double *P[2] = {(double *)workspace_dev, (double *)workspace_dev + ((long long)g.hs[1] * g.ws[1] + 1) / 2 * 2};
+    const LiftPlanes pl = lift_planes(g, workspace_dev);
     // explicit ping-pong: a launch reads `in` (the LL of the level above) and writes the other plane
     const double *in = nullptr;
     int nb = 0;
-    const bool nofuse = lift_nofuse();
+    const bool nofuse = !sc.lift_fused;
     for (int r = levels; r >= 1;) {
         const int h = g.hs[r], w = g.ws[r];
         const bool coarsest = r == levels;
-        double *out = P[nb];
+        double *out = pl.P[nb];
         // levels r and r - 1 in one launch (lift_inv21_kernel) when each LL is exactly twice
         // the one above both ways (C3: levels 4 + 3 and 2 + 1)
         const int hl = r >= 2 ? g.hs[r - 1] : 0, wl = r >= 2 ? g.ws[r - 1] : 0;
@@ -2202,7 +2168,7 @@ int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t 
             const int n_strips = (w + lift::kV2 - 1) / lift::kV2;
             const long long per_band = n_frames * n_strips;
             // a band of B upper-level rows: B + 6 of its steps, 2 B + 4 lower-level ones
-            const int brows = lift_brows(per_band, h, resident_slots(kern, lift::kNT), 2, 12);
+            const int brows = lift_brows(kern, per_band, h, 2, 12);
             const int n_bands = (h + brows - 1) / brows;
             const long long grid = per_band * n_bands;
             if (grid > 0x7fffffffLL) return set_error(VCF_ERR_INVALID, "too many frames per call");
@@ -2226,7 +2192,7 @@ int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t 
         const long long per_band = n_frames * n_strips;
         auto kern = coarsest ? (rgb ? lift::lift_inv_kernel<true, true> : lift::lift_inv_kernel<true, false>)
                              : (rgb ? lift::lift_inv_kernel<false, true> : lift::lift_inv_kernel<false, false>);
-        const int brows = lift_brows(per_band, h, resident_slots(kern, lift::kNT));
+        const int brows = lift_brows(kern, per_band, h);
         const int n_bands = (h + brows - 1) / brows, n_edge = n_strips - n_int;
         const int brows_e = brows, n_bands_e = n_bands;
         const long long edge_blocks = n_frames * n_edge * n_bands_e;
@@ -2244,6 +2210,33 @@ int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t 
     }
     return VCF_OK;
 }
+
+#ifndef VCF_DWT_SCHED_BUILD
+// the product entry points: the library's schedule
+int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
+                      int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
+{
+    return dwt_encode(DwtSchedule{}, rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev, stream);
+}
+
+int vcf_dwt_dz_decode(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
+                      int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
+{
+    return dwt_decode(DwtSchedule{}, packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev, stream);
+}
+
+int vcf_dwt_dz_encode_lift(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
+                           int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
+{
+    return dwt_encode_lift(DwtSchedule{}, rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev, stream);
+}
+
+int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
+                           int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
+{
+    return dwt_decode_lift(DwtSchedule{}, packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev, stream);
+}
+#endif
 
 }  // extern "C"
 #endif  // VCF_DWT_KERNELS_ONLY

@@ -93,25 +93,35 @@ def decode_device(packed: DeviceBuffer, n: int, H: int, W: int, wavelet: int, le
            workspace.ptr, None if stream is None else stream.handle)
 
 
+def _run(name: str, variant: int, lifting: bool, schedule, *args) -> None:
+    """The product entry point `name` (its lifting form), or the A/B library's
+    variant of it, or -- schedule: a mapping of vcf_dwt_schedule's field names
+    (include/vcf_amd_ab.h) -- the A/B library's build of the product code under
+    that kernel schedule (A/B records and cross-checks, not the product path;
+    unknown field names raise ValueError before the call)."""
+    if variant and (lifting or schedule is not None):
+        raise ValueError("lifting and schedule apply to the product code, not to an A/B variant")
+    if schedule is not None:
+        L.call_ab(_entry(name, lifting) + "_sched", ctypes.byref(L.DwtSchedule(**schedule)), *args)
+    elif variant == 0:
+        L.call(_entry(name, lifting), *args)
+    else:
+        L.call_ab(name + "_variant", int(variant), *args)
+
+
 def encode(rgb: np.ndarray, wavelet: str = "db5", levels: int = 5, Q: int = 32, variant: int = 0,
-           lifting: bool = False):
+           lifting: bool = False, schedule=None):
     """HxWx3 u8 (or N of them) -> list of {subband name: indices} per frame.
     variant: 0 the product kernels; any other value a variant of the A/B library
     (include/vcf_amd_ab.h: 1 fused level kernels, 2 separable kernels, 6 strip kernels on every
-    level, ...; A/B records and cross-checks, not the product path)."""
+    level, ...; A/B records and cross-checks, not the product path).  schedule: see _run."""
     f = _frames(rgb, "rgb")
     n, H, W, _ = f.shape
     _, pb, wb = layout(H, W, levels)
     din, dout, dws = DeviceBuffer.from_array(f), DeviceBuffer(n * pb), DeviceBuffer(n * wb)
     try:
-        if variant and lifting:
-            raise ValueError("lifting is a product entry point, not an A/B variant")
-        if variant == 0:
-            L.call(_entry("vcf_dwt_dz_encode", lifting), din.ptr, n, H, W, wavelet_index(wavelet), levels, int(Q),
-                   dout.ptr, dws.ptr, None)
-        else:
-            L.call_ab("vcf_dwt_dz_encode_variant", int(variant), din.ptr, n, H, W, wavelet_index(wavelet), levels,
-                      int(Q), dout.ptr, dws.ptr, None)
+        _run("vcf_dwt_dz_encode", variant, lifting, schedule, din.ptr, n, H, W, wavelet_index(wavelet), levels, int(Q),
+             dout.ptr, dws.ptr, None)
         packed = dout.download(np.empty((n, pb), np.uint8))
     finally:
         din.free()
@@ -121,7 +131,7 @@ def encode(rgb: np.ndarray, wavelet: str = "db5", levels: int = 5, Q: int = 32, 
 
 
 def decode(subbands, H: int, W: int, wavelet: str = "db5", levels: int = 5, Q: int = 32,
-           variant: int = 0, lifting: bool = False) -> np.ndarray:
+           variant: int = 0, lifting: bool = False, schedule=None) -> np.ndarray:
     """{name: indices} (or a list of them) -> u8 RGB (2*ceil(H/2) x 2*ceil(W/2) x 3 each)."""
     single = isinstance(subbands, dict)
     sets = [subbands] if single else list(subbands)
@@ -131,14 +141,8 @@ def decode(subbands, H: int, W: int, wavelet: str = "db5", levels: int = 5, Q: i
     Ho, Wo = 2 * shapes[0][0], 2 * shapes[0][1]
     din, dout, dws = DeviceBuffer.from_array(packed), DeviceBuffer(n * Ho * Wo * 3), DeviceBuffer(n * wb)
     try:
-        if variant and lifting:
-            raise ValueError("lifting is a product entry point, not an A/B variant")
-        if variant == 0:
-            L.call(_entry("vcf_dwt_dz_decode", lifting), din.ptr, n, H, W, wavelet_index(wavelet), levels, int(Q),
-                   dout.ptr, dws.ptr, None)
-        else:
-            L.call_ab("vcf_dwt_dz_decode_variant", int(variant), din.ptr, n, H, W, wavelet_index(wavelet), levels,
-                      int(Q), dout.ptr, dws.ptr, None)
+        _run("vcf_dwt_dz_decode", variant, lifting, schedule, din.ptr, n, H, W, wavelet_index(wavelet), levels, int(Q),
+             dout.ptr, dws.ptr, None)
         out = dout.download(np.empty((n, Ho, Wo, 3), np.uint8))
     finally:
         din.free()
