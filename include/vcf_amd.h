@@ -147,6 +147,46 @@ int vcf_mdct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int3
 int vcf_mdct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                        int32_t Q, uint32_t flags, uint8_t *rgb_dev, void *stream);
 
+/* ---- 2D-KLT (2D-KLT.py) --------------------------------------------------
+ * A Karhunen-Loeve basis of the B x B blocks, learned per frame and colour
+ * channel: D = B * B values per block, N blocks per frame after the pad.
+ * Common to the three device entry points: arguments are checked before any
+ * device work; 2 <= block_size <= 16 (17 and up: VCF_ERR_UNSUPPORTED; 1, where
+ * the reference's covariance is a scalar: VCF_ERR_INVALID); H, W >= 1 with
+ * N >= 2 (a frame of one block has no covariance: VCF_ERR_INVALID);
+ * n_frames >= 1; work is enqueued on the caller's stream. */
+
+/* Padded frame shape of 2D-KLT.py:393-411: Hp = ceil(H / B) * B, centred zero
+ * pad with pad_top = (Hp - H) / 2 (the rest below), likewise for the width.
+ * Host only. */
+int vcf_klt_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp, int32_t *Wp, int32_t *pad_top,
+                         int32_t *pad_left);
+
+/* Exact second moments of the blocks: per frame and channel S1 (int64[D]) =
+ * sum of s and S2 (int64[D][D], full symmetric) = sum of s s^T over the N
+ * blocks, s = 4 x, x = the YCoCg value after the zero pad and -128 (s is an
+ * integer, |s| <= 512).  s1_dev: n_frames x 3 x D, s2_dev: n_frames x 3 x D x
+ * D.  Integer arithmetic throughout: the result does not depend on tiling,
+ * order or batch.  The covariance is (S2 - S1 S1^T / N) / (16 (N - 1)). */
+int vcf_klt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
+                    int64_t *s1_dev, int64_t *s2_dev, void *stream);
+
+/* 2D-KLT.py encode_fn :515-628 between the image read and the entropy codec,
+ * with the basis given: weights_f64_dev is n_frames x 3 x D x D float64, row k
+ * = basis vector k.  Zero pad, -128, YCoCg, coef[k] = sum_j W[k][j] x[j] in
+ * float64 (j ascending, FMA), / Q (float64 division), truncated, +128,
+ * WRAPPED to u8 (not clipped); subband layout unless VCF_DCT_NO_SUBBANDS (the
+ * only flag).  1 <= Q <= 32767.  k_dev: n_frames x Hp x Wp x 3. */
+int vcf_klt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
+                      uint32_t flags, const double *weights_f64_dev, uint8_t *k_dev, void *stream);
+
+/* The inverse, 2D-KLT.py decode_fn :738-809: weights_f32_dev is n_frames x 3 x
+ * D x D float32 as stored in {out}_weights.npz, widened on the device;
+ * rec[j] = sum_k W[k][j] (Q (k - 128)) (int16 dequantizer; k ascending, FMA),
+ * inverse YCoCg and +128 in float64, clip, truncate, padding removed. */
+int vcf_klt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
+                      uint32_t flags, const float *weights_f32_dev, uint8_t *rgb_dev, void *stream);
+
 /* 1 if block_size has a HIP transform: every 1 <= B <= 4096 -- compiled
  * kernels for the 38 5-smooth B <= 128 (every -L candidate 2, 4, ..., 128,
  * 2D-DCT.py:536), run-time-length kernels for the rest: rfftp plans with the

@@ -97,6 +97,10 @@ SIGNATURES = {
     "vcf_mdct_padded_shape": [_I32, _I32, _I32, _PI32, _PI32, _PI32, _PI32],
     "vcf_mdct_dz_encode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P],
     "vcf_mdct_dz_decode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P],
+    "vcf_klt_padded_shape": [_I32, _I32, _I32, _PI32, _PI32, _PI32, _PI32],
+    "vcf_klt_moments": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],
+    "vcf_klt_dz_encode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P, _P],
+    "vcf_klt_dz_decode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P, _P],
     "vcf_ycrcb_from_rgb": [_P, _I64, _P, _P],
     "vcf_ycrcb_to_rgb": [_P, _I64, _P, _P],
     "vcf_ycrcb_dz_encode": [_P, _I64, _I32, _P, _P],

@@ -1,0 +1,14 @@
+#!/usr/bin/env python3
+"""Drop-in for `python 2D-KLT.py [-g] {encode,decode} ...` (src/2D-KLT.py):
+YCoCg + a learned B x B block transform (KLT) + deadzone + TIFF, the hot span on the GPU."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+
+from vcf_amd.codec import parser as P  # noqa: E402
+from vcf_amd.codec.main import main  # noqa: E402
+from vcf_amd.codec.klt2d import CoDec  # noqa: E402
+
+if __name__ == "__main__":
+    main(P.klt_parser(entropy=P.entropy_of(sys.argv[1:])), CoDec)

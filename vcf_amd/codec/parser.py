@@ -190,6 +190,18 @@ def add_mdct(enc, dec):
                        default=False)
 
 
+def add_klt(enc, dec):
+    """2D-KLT.py:64-70 (-B is named block_size here, not block_size_DCT; no -p, no -L)."""
+    for p in (enc, dec):
+        p.add_argument("-B", "--block_size", type=int_or_str,
+                       help=f"Block size (default: {DEFAULT_BLOCK_SIZE})", default=DEFAULT_BLOCK_SIZE)
+        p.add_argument("-t", "--color_transform", type=int_or_str,
+                       help=f"Color transform (default: \"{DEFAULT_CT}\")", default=DEFAULT_CT)
+        p.add_argument("-x", "--disable_subbands", action="store_true",
+                       help="Disable the coefficients reordering in subbands (default: \"False\")",
+                       default=False)
+
+
 def add_dwt(enc, dec):
     """2D-DWT.py:25-31."""
     for p in (enc, dec):
@@ -235,6 +247,18 @@ def mdct_parser(description: str = "Exploiting spatial redundancy with the Modif
     return p
 
 
+def klt_parser(description: str = "Exploiting spatial redundancy with a learned block transform (the "
+                                  "Karhunen-Loeve transform of the image's blocks).", entropy: str = DEFAULT_EIC):
+    """`python 2D-KLT.py ...` (2D-KLT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py)."""
+    p, enc, dec = base_parser(description)
+    add_klt(enc, dec)
+    add_ycocg(enc, dec)
+    add_deadzone(enc, dec)
+    add_filter(enc, dec, entropy)
+    add_eic(enc, dec)
+    return p
+
+
 def dwt_parser(description: str = "Exploiting spatial redundancy with the 2D dyadic Discrete Wavelet "
                                   "Transform.", entropy: str = DEFAULT_EIC):
     """`python 2D-DWT.py ...` (2D-DWT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py)."""
@@ -256,6 +280,8 @@ def iii_parser(description: str = "III coding: runs a 2D image codec for each im
         add_dwt(enc, dec)
     elif transform == "2D-MDCT":
         add_mdct(enc, dec)
+    elif transform == "2D-KLT":
+        add_klt(enc, dec)
     else:
         add_dct(enc, dec)
     add_ycocg(enc, dec)
