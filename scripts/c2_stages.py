@@ -1,5 +1,5 @@
 """C2 (1080p frame, YCoCg + 2D-DCT B=8 + deadzone + CBAAC) per-stage breakdown
-of CoDec.encode_fn (vcf_amd/codec/dct2d.py:268-294), the stages timed one by
+of CoDec.encode_fn (vcf_amd/codec/blockcodec.py, dct2d._encode_one), the stages timed one by
 one with the same calls encode_fn makes:
 
   read     encode_read_fn: the PNG decode (native reader, codec/eic.py)

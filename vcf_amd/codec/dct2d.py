@@ -35,62 +35,10 @@ import numpy as np
 
 from .. import dct as D
 from ..device import DeviceBuffer
-from .eic import CoDec as EICCoDec
-from .quantizers import LloydMaxQuantizer
+from .blockcodec import BlockCoDec
+from .entropy import ENTROPY_CODECS, _tcbaac_prior, make_entropy, register_entropy_codec  # noqa: F401  (imported from here)
+from .quantizers import LloydMaxQuantizer, make_quantizer  # noqa: F401
 from .tiff import TIFFCodec
-
-
-def _cbaac(args=None):
-    from ..cbaac import CBAACCodec
-    return CBAACCodec(getattr(args, "order", 0) if args is not None else 0)
-
-
-def _cbahc(args=None):
-    from ..cbahc import CBAHCCodec
-    return CBAHCCodec(getattr(args, "order", 0) if args is not None else 0)
-
-
-def _tcbaac(args=None):
-    from ..tcbaac import DEFAULT_SEG, TiledCBAACCodec
-    return TiledCBAACCodec(getattr(args, "order", 0) if args is not None else 0,
-                           getattr(args, "segment_symbols", DEFAULT_SEG) if args is not None else DEFAULT_SEG)
-
-
-def _tcbaac_prior(args=None):
-    from ..tcbaac import CLASS_SEG, PRIOR_CLASSES, TiledCBAACCodec
-    return TiledCBAACCodec(getattr(args, "order", 0) if args is not None else 0,
-                           getattr(args, "segment_symbols", CLASS_SEG) if args is not None else CLASS_SEG, prior=True,
-                           nclass=PRIOR_CLASSES)
-
-
-# TCBAAC: CBAAC in independent segments on the GPU (vcf_amd/tcbaac.py, a new container);
-# TCBAACP: the same with every segment's models seeded by a prior row of the frame: 8 rows, one per run of
-# segments (about one subband row each), 4096-symbol segments (container version 3)
-ENTROPY_CODECS = {"TIFF": TIFFCodec, "CBAAC": _cbaac, "CBAHC": _cbahc, "TCBAAC": _tcbaac, "TCBAACP": _tcbaac_prior}
-
-
-def register_entropy_codec(name, cls):
-    ENTROPY_CODECS[name] = cls
-
-
-def make_entropy(args):
-    """The entropy codec named by -c (no_filter.py:14-21)."""
-    ec_name = getattr(args, "entropy_image_codec", "TIFF")
-    if ec_name not in ENTROPY_CODECS:
-        raise NotImplementedError(f"entropy codec {ec_name!r} (have: {sorted(ENTROPY_CODECS)})")
-    maker = ENTROPY_CODECS[ec_name]
-    return maker(args) if maker in (_cbaac, _cbahc, _tcbaac, _tcbaac_prior) else maker()
-
-
-def make_quantizer(args):
-    """None for -a deadzone (fused into the transform kernels), else the LloydMax plug-in."""
-    quant = getattr(args, "quantizer", "deadzone")
-    if quant == "deadzone":
-        return None
-    if quant == "LloydMax":
-        return LloydMaxQuantizer(int(getattr(args, "QSS", 32)), int(getattr(args, "min_val", 0)),
-                                 int(getattr(args, "max_val", 255)))
-    raise NotImplementedError(f"quantizer {quant!r}: deadzone and LloydMax are on the HIP path")
 
 
 class _Zipped:
@@ -105,34 +53,16 @@ class _Zipped:
         return imread_bytes(self.data)
 
 
-def _flags(args) -> int:
-    return D.flags_from(bool(getattr(args, "disable_subbands", False)),
-                        bool(getattr(args, "perceptual_quantization", False)))
-
-
-class CoDec(EICCoDec):
+class CoDec(BlockCoDec):
     """2D-DCT.CoDec (2D-DCT.py:50-579) over the YCoCg / deadzone / no_filter /
     <entropy codec> chain."""
 
+    BLOCK_SIZE_ARG = "block_size_DCT"
+    COLOR_REFUSAL = "color transform {!r}: YCoCg (and YCrCb, which 2D-DCT.py runs as YCoCg) are on the HIP path"
+    FRAME_ERROR = "Input image must be a 3D array (height, width, channels)."
+
     def __init__(self, args):
         super().__init__(args)
-        self.block_size = int(getattr(args, "block_size_DCT", 8))
-        ct = getattr(args, "color_transform", "YCoCg")
-        if ct not in ("YCoCg", "YCrCb"):
-            raise NotImplementedError(f"color transform {ct!r}: YCoCg (and YCrCb, which 2D-DCT.py runs as "
-                                      "YCoCg) are on the HIP path")
-        self.lm = make_quantizer(args)
-        filt = getattr(args, "filter", "no_filter")
-        if not self.encoding and filt != "no_filter":
-            raise NotImplementedError(f"filter {filt!r}: only no_filter is on the HIP path")
-        if not D.block_size_supported(self.block_size):
-            raise NotImplementedError(f"block size {self.block_size}: the HIP path covers 1 <= B <= 4096")
-        self.entropy = make_entropy(args)
-        self.file_extension = self.entropy.file_extension
-        self.QSS = int(getattr(args, "QSS", 32))
-        self.offset = 128 if self.lm is None else 0    # 2D-DCT.py:106-109
-        self.flags = _flags(args)
-        self.original_shape = None
         self.Lambda = None
         if self.encoding and getattr(args, "Lambda", None) is not None and self.lm is not None:
             raise NotImplementedError("-L with -a LloydMax: the search's quantizer calls are not on the HIP path")
@@ -153,12 +83,12 @@ class CoDec(EICCoDec):
             self._staged = None
         super().bye()
 
-    # entropy stage (TIFF.py / CBAAC.py surface)
-    def compress(self, img):
-        return self.entropy.compress(img)
+    def _quantizer(self, args):
+        return make_quantizer(args)
 
-    def decompress(self, codestream):
-        return self.entropy.decompress(codestream)
+    def _check_block_size(self):
+        if not D.block_size_supported(self.block_size):
+            raise NotImplementedError(f"block size {self.block_size}: the HIP path covers 1 <= B <= 4096")
 
     # 2D-DCT.py:187-266 semantics, used by callers that pad/crop themselves
     def pad_and_center_to_multiple_of_block_size(self, img):
@@ -220,12 +150,6 @@ class CoDec(EICCoDec):
         return self.block_size
 
     # ---- the hot path -------------------------------------------------------
-    def _check_frame(self, img):
-        if img.ndim != 3:
-            raise ValueError("Input image must be a 3D array (height, width, channels).")
-        if img.dtype != np.uint8 or img.shape[2] != 3:
-            raise NotImplementedError(f"{img.dtype} x{img.shape[2]} images: the HIP path takes u8 RGB")
-
     def _deadzone_only(self, what):
         if self.lm is not None:
             raise NotImplementedError(f"{what} with -a LloydMax (use encode_fn/decode_fn)")
@@ -280,17 +204,23 @@ class CoDec(EICCoDec):
         return D.decode(np.ascontiguousarray(k, dtype=np.uint8), H, W, self.QSS, self.flags,
                         self.block_size)
 
-    def encode_fn(self, in_fn, out_fn):
-        img = self.encode_read_fn(in_fn)
+    def _encode_one(self, img):
         if self.lm is not None:
-            cs = self.compress(self.encode_lm(img))
-        elif hasattr(self.entropy, "compress_device"):
-            cs = self._encode_compress_device(img)
-        else:
-            cs = self.compress(self.encode_indices(img))
+            return self.compress(self.encode_lm(img)), None
+        if hasattr(self.entropy, "compress_device"):
+            return self._encode_compress_device(img), None
+        return self.compress(self.encode_indices(img)), None
+
+    def _decode_one(self, k, shape, extra):
+        return self.decode_lm(k, shape) if self.lm is not None else self.decode_indices(k, shape)
+
+    def _write_side(self, out_fn, shape, extra):
         with open(f"{out_fn}_shape.bin", "wb") as f:
-            f.write(struct.pack("iii", *self.original_shape))
-        return self.encode_write_fn(cs, out_fn)
+            f.write(struct.pack("iii", *shape))
+
+    def _read_side(self, fn):
+        with open(f"{fn}_shape.bin", "rb") as f:
+            return struct.unpack("iii", f.read(12)), None
 
     def _encode_compress_device(self, img):
         """GPU-resident entropy stage: the indices stay in HBM between the
@@ -308,79 +238,9 @@ class CoDec(EICCoDec):
                             block_size=self.block_size)
             return self.entropy.compress_device(k, (Hp, Wp, 3))
 
-    def encode(self, in_fn="/tmp/original.png", out_fn="/tmp/encoded"):
-        # 2D-DCT.py:374-375: the reference's encode() ignores -o/-e
-        return self.encode_fn(in_fn, out_fn)
-
-    def decode_fn(self, in_fn, out_fn):
-        codestream = self.decode_read_fn(in_fn)
-        with open(f"{in_fn}_shape.bin", "rb") as f:
-            self.original_shape = struct.unpack("iii", f.read(12))
-        k = self.decompress(codestream)
-        if self.lm is not None:
-            y = self.decode_lm(k, self.original_shape)
-        else:
-            y = self.decode_indices(k, self.original_shape)
-        return self.decode_write_fn(y, out_fn)
-
-    def decode(self, in_fn="/tmp/encoded", out_fn="/tmp/decoded.png"):
-        return self.decode_fn(in_fn, out_fn)
-
-    # ---- batched frames (III runner): one launch per batch of equal shapes --
-    def encode_fns(self, pairs, batch: int = 64, io_threads: int = 16):
-        """encode_fn over (in_fn, out_fn) pairs; returns the bytes written per
-        frame.  A three-stage pipeline: host threads
-        decode the PNGs of the next two batches while the GPU encodes this
-        one (one launch per group of equal shapes), and TIFF deflate + file
-        writes of the previous batches run behind it on the same pool.  When
-        every input is a PNG of one shape the natively decodable kind, the
-        frames go through pinned double-buffered slots (staging.StagedEncoder):
-        decoded straight into page-locked memory, async copies, no stacking."""
-        pairs = list(pairs)
-        if not pairs:
-            return []
-        if self.lm is not None:   # one histogram and design per frame: frame by frame
-            return [self.encode_fn(i, o) for i, o in pairs]
-        staged = self._encode_fns_staged(pairs, batch, io_threads)
-        if staged is not None:
-            return staged
-        sizes = [0] * len(pairs)
-        batches = [pairs[b0:b0 + batch] for b0 in range(0, len(pairs), batch)]
-
-        def _read(p):
-            img = self.encode_read_fn(p[0])
-            self._check_frame(img)
-            return img
-
-        def _write(out_fn, img_shape, k):
-            with open(f"{out_fn}_shape.bin", "wb") as f:
-                f.write(struct.pack("iii", *img_shape))
-            return self.encode_write_fn(self.compress(k), out_fn)
-
-        with ThreadPoolExecutor(max_workers=io_threads) as pool:
-            reads = {}
-            for b in range(min(2, len(batches))):
-                reads[b] = [pool.submit(_read, p) for p in batches[b]]
-            writes = []
-            for b, chunk in enumerate(batches):
-                imgs = [f.result() for f in reads.pop(b)]
-                if b + 2 < len(batches):
-                    reads[b + 2] = [pool.submit(_read, p) for p in batches[b + 2]]
-                groups = {}
-                for i, img in enumerate(imgs):
-                    groups.setdefault(img.shape, []).append(i)
-                ks = [None] * len(chunk)
-                for shape, idx in groups.items():
-                    out = D.encode(np.stack([imgs[i] for i in idx]), self.QSS, self.flags, self.block_size)
-                    for j, i in enumerate(idx):
-                        ks[i] = out[j]
-                b0 = b * batch
-                for i in range(len(chunk)):
-                    writes.append((b0 + i, pool.submit(_write, chunk[i][1], imgs[i].shape, ks[i])))
-                self.original_shape = imgs[-1].shape
-            for i, f in writes:
-                sizes[i] = f.result()
-        return sizes
+    # ---- batched frames (III runner) ------------------------------------------
+    def _encode_group(self, frames, shape):
+        return [(k, None) for k in D.encode(frames, self.QSS, self.flags, self.block_size)]
 
     def _encode_fns_staged(self, pairs, batch, io_threads):
         from .. import staging
@@ -464,61 +324,23 @@ class CoDec(EICCoDec):
         self.original_shape = (H, W, 3)
         return sizes
 
-    def decode_fns(self, pairs, batch: int = 64, io_threads: int = 16):
-        """decode_fn over (in_fn, out_fn) pairs, pipelined like encode_fns: the
-        next two batches' TIFFs are inflated on host threads while the GPU
-        decodes this one, and the PNG writes of earlier batches run behind."""
-        pairs = list(pairs)
-        if not pairs:
-            return []
-        if self.lm is not None:
-            return [self.decode_fn(i, o) for i, o in pairs]
-        sizes = [0] * len(pairs)
-        batches = [pairs[b0:b0 + batch] for b0 in range(0, len(pairs), batch)]
-        # -c TIFF (the default): a batch's strips are inflated on the GPU straight into
-        # the index frames the decode kernel reads (vcf_amd/zlib_gpu.py StripInflater,
-        # zlib.decompress's semantics); the host threads only read the files
-        gpu_tiff = isinstance(self.entropy, TIFFCodec) and TIFFCodec.gpu_batches and self.block_size == 8
+    def _decode_item(self, cs, shp):
+        """-c TIFF (the default) at B = 8: the host threads only read the files; a batch's strips
+        are inflated on the GPU straight into the index frames the decode kernel reads
+        (vcf_amd/zlib_gpu.py StripInflater, zlib.decompress's semantics)."""
+        if isinstance(self.entropy, TIFFCodec) and TIFFCodec.gpu_batches and self.block_size == 8:
+            from .tiff import tiff_strips
+            info = tiff_strips(cs)
+            Hp, Wp = D.padded_shape(shp[0], shp[1], self.block_size)
+            if info is not None and tuple(info[0]) == (Hp, Wp, 3) and info[1] == np.uint8:
+                return _Zipped(cs, info)
+        return self.decompress(cs)
 
-        def _read(p):
-            cs = self.decode_read_fn(p[0])
-            with open(f"{p[0]}_shape.bin", "rb") as f:
-                shp = struct.unpack("iii", f.read(12))
-            if gpu_tiff:
-                from .tiff import tiff_strips
-                info = tiff_strips(cs)
-                Hp, Wp = D.padded_shape(shp[0], shp[1], self.block_size)
-                if info is not None and tuple(info[0]) == (Hp, Wp, 3) and info[1] == np.uint8:
-                    return _Zipped(cs, info), shp
-            return self.decompress(cs), shp
-
-        with ThreadPoolExecutor(max_workers=io_threads) as pool:
-            reads = {b: [pool.submit(_read, p) for p in batches[b]] for b in range(min(2, len(batches)))}
-            writes = []
-            for b, chunk in enumerate(batches):
-                got = [f.result() for f in reads.pop(b)]
-                if b + 2 < len(batches):
-                    reads[b + 2] = [pool.submit(_read, p) for p in batches[b + 2]]
-                groups = {}
-                for i, (k, shp) in enumerate(got):
-                    groups.setdefault(tuple(shp), []).append(i)
-                ys = [None] * len(chunk)
-                for shp, idx in groups.items():
-                    if all(isinstance(got[i][0], _Zipped) for i in idx):
-                        out = self._decode_zipped([got[i][0] for i in idx], shp)
-                    else:
-                        ks = [got[i][0] if not isinstance(got[i][0], _Zipped) else got[i][0].host()
-                              for i in idx]
-                        out = D.decode(np.stack(ks), shp[0], shp[1], self.QSS, self.flags, self.block_size)
-                    for j, i in enumerate(idx):
-                        ys[i] = out[j]
-                self.original_shape = got[-1][1]
-                b0 = b * batch
-                for i in range(len(chunk)):
-                    writes.append((b0 + i, pool.submit(self.decode_write_fn, ys[i], chunk[i][1])))
-            for i, f in writes:
-                sizes[i] = f.result()
-        return sizes
+    def _decode_group(self, items, shp, extras):
+        if all(isinstance(k, _Zipped) for k in items):
+            return self._decode_zipped(items, shp)
+        ks = [k.host() if isinstance(k, _Zipped) else k for k in items]
+        return D.decode(np.stack(ks), shp[0], shp[1], self.QSS, self.flags, self.block_size)
 
     def _decode_zipped(self, zs, shp):
         """n TIFFs of one shape -> n decoded frames: every strip inflated on the GPU
@@ -549,22 +371,3 @@ class CoDec(EICCoDec):
         drgb.download(res, st)
         st.synchronize()
         return res
-
-    # ---- quantizer surface (deadzone.py:95-124) -----------------------------
-    def quantize_decom(self, decom):
-        return self.quantize(decom)
-
-    def dequantize_decom(self, decom_k):
-        return self.dequantize(decom_k)
-
-    def quantize(self, img, fn="/tmp/encoded"):
-        if self.lm is not None:
-            return self.lm.quantize(img, fn)
-        from .. import quant
-        return quant.deadzone_quantize(img, self.QSS)
-
-    def dequantize(self, k, fn="/tmp/encoded"):
-        if self.lm is not None:
-            return self.lm.dequantize(k, fn)
-        from .. import quant
-        return quant.deadzone_dequantize(k, self.QSS)

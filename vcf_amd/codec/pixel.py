@@ -18,9 +18,9 @@ import numpy as np
 
 from .. import plugins as PL
 from ..device import DeviceBuffer
-from .dct2d import make_entropy, make_quantizer
 from .eic import CoDec as EICCoDec
-from .quantizers import LloydMaxQuantizer
+from .entropy import make_entropy
+from .quantizers import LloydMaxQuantizer, make_quantizer
 
 
 class _PixelCoDec(EICCoDec):

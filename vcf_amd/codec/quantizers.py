@@ -86,3 +86,14 @@ class LloydMaxQuantizer:
 
     def dequantize(self, k, fn=SIDE_PREFIX):
         return self.dequantize_fn(k, fn)
+
+
+def make_quantizer(args):
+    """None for -a deadzone (fused into the transform kernels), else the LloydMax plug-in."""
+    quant = getattr(args, "quantizer", "deadzone")
+    if quant == "deadzone":
+        return None
+    if quant == "LloydMax":
+        return LloydMaxQuantizer(int(getattr(args, "QSS", 32)), int(getattr(args, "min_val", 0)),
+                                 int(getattr(args, "max_val", 255)))
+    raise NotImplementedError(f"quantizer {quant!r}: deadzone and LloydMax are on the HIP path")

@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._blockio import check_input, flags_from, frames_u8 as _frames, output, round_trip
 from ._lib import VCF_DCT_NO_SUBBANDS, VCF_DCT_PERCEPTUAL, call, call_ab
 from .device import DeviceBuffer, _h
 
@@ -35,10 +36,6 @@ def padded_shape(H: int, W: int, block_size: int = 8):
     return hp.value, wp.value
 
 
-def flags_from(disable_subbands: bool = False, perceptual: bool = False) -> int:
-    return (VCF_DCT_NO_SUBBANDS if disable_subbands else 0) | (VCF_DCT_PERCEPTUAL if perceptual else 0)
-
-
 def encode_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, Q: int = 32, flags: int = 0,
                   out: DeviceBuffer | None = None, stream=None, block_size: int = 8,
                   variant: int = 0) -> DeviceBuffer:
@@ -48,12 +45,8 @@ def encode_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, Q: int = 32,
     other value a kernel variant of the A/B library (include/vcf_amd_ab.h: A/B records and
     cross-checks, not the product path)."""
     Hp, Wp = padded_shape(H, W, block_size)
-    if rgb.nbytes < n_frames * H * W * 3:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * Hp * Wp * 3)
-    elif out.nbytes < n_frames * Hp * Wp * 3:
-        raise ValueError("output buffer too small")
+    check_input(rgb, n_frames * H * W * 3)
+    out = output(out, n_frames * Hp * Wp * 3)
     if variant == -1:
         call("vcf_dct_dz_encode_any", rgb.ptr, n_frames, H, W, block_size, int(Q), flags, out.ptr, _h(stream))
     elif variant == 0:
@@ -70,12 +63,8 @@ def decode_device(k: DeviceBuffer, n_frames: int, H: int, W: int, Q: int = 32, f
     """variant: 0 the product kernels, -1 the generic-B kernels (any supported B, 8 included),
     any other value a decode variant of the A/B library (include/vcf_amd_ab.h)."""
     Hp, Wp = padded_shape(H, W, block_size)
-    if k.nbytes < n_frames * Hp * Wp * 3:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * H * W * 3)
-    elif out.nbytes < n_frames * H * W * 3:
-        raise ValueError("output buffer too small")
+    check_input(k, n_frames * Hp * Wp * 3)
+    out = output(out, n_frames * H * W * 3)
     if variant == -1:
         call("vcf_dct_dz_decode_any", k.ptr, n_frames, H, W, block_size, int(Q), flags, out.ptr, _h(stream))
     elif variant == 0:
@@ -86,62 +75,45 @@ def decode_device(k: DeviceBuffer, n_frames: int, H: int, W: int, Q: int = 32, f
     return out
 
 
-def _frames(a: np.ndarray, what: str) -> np.ndarray:
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        raise TypeError(f"{what} must be uint8, got {a.dtype}")
-    if a.ndim == 3:
-        a = a[None]
-    if a.ndim != 4 or a.shape[3] != 3:
-        raise ValueError("Input image must be a 3D array (height, width, channels).")
-    return np.ascontiguousarray(a)
-
-
 def encode(rgb: np.ndarray, Q: int = 32, flags: int = 0, block_size: int = 8,
            variant: int = 0) -> np.ndarray:
     """Host convenience: HxWx3 (or NxHxWx3) u8 -> HpxWpx3 (NxHpxWpx3) u8 indices."""
-    single = np.asarray(rgb).ndim == 3
     f = _frames(rgb, "rgb")
     n, H, W, _ = f.shape
-    Hp, Wp = padded_shape(H, W, block_size)
-    din = DeviceBuffer.from_array(f)
-    dout = encode_device(din, n, H, W, Q, flags, block_size=block_size, variant=variant)
-    res = dout.download(np.empty((n, Hp, Wp, 3), np.uint8))
-    din.free()
-    dout.free()
-    return res[0] if single else res
+    return round_trip(f, np.asarray(rgb).ndim == 3,
+                      lambda din: encode_device(din, n, H, W, Q, flags, block_size=block_size, variant=variant),
+                      padded_shape(H, W, block_size) + (3,))
 
 
 def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, block_size: int = 8,
            variant: int = 0) -> np.ndarray:
     """Host convenience: HpxWpx3 (or N...) u8 indices -> HxWx3 u8 reconstruction."""
-    single = np.asarray(k).ndim == 3
     f = _frames(k, "k")
-    n = f.shape[0]
     Hp, Wp = padded_shape(H, W, block_size)
     if f.shape[1:3] != (Hp, Wp):
         raise ValueError(f"index frames {f.shape[1:3]} do not match {(Hp, Wp)} for {H}x{W}")
-    din = DeviceBuffer.from_array(f)
-    dout = decode_device(din, n, H, W, Q, flags, block_size=block_size, variant=variant)
-    res = dout.download(np.empty((n, H, W, 3), np.uint8))
-    din.free()
-    dout.free()
-    return res[0] if single else res
+    return round_trip(f, np.asarray(k).ndim == 3,
+                      lambda din: decode_device(din, len(f), H, W, Q, flags, block_size=block_size, variant=variant),
+                      (H, W, 3))
+
+
+def _k32(name: str, nbytes: int, n: int, H: int, W: int, block_size: int, Q: int, flags: int):
+    """The launch of an int32 kernel of the -L search, for round_trip."""
+    def launch(din):
+        dout = DeviceBuffer(nbytes)
+        call(name, din.ptr, n, H, W, block_size, int(Q), flags, dout.ptr, None)
+        return dout
+    return launch
 
 
 def encode_k32(rgb: np.ndarray, Q: int = 32, flags: int = 0, block_size: int = 8) -> np.ndarray:
     """-L analysis (2D-DCT.py:538-545): HxWx3 (or N...) u8 -> HpxWpx3 int32 k, before +128/uint8."""
-    single = np.asarray(rgb).ndim == 3
     f = _frames(rgb, "rgb")
     n, H, W, _ = f.shape
     Hp, Wp = padded_shape(H, W, block_size)
-    din = DeviceBuffer.from_array(f)
-    dout = DeviceBuffer(n * Hp * Wp * 3 * 4)
-    call("vcf_dct_dz_encode_k32", din.ptr, n, H, W, block_size, int(Q), flags, dout.ptr, None)
-    res = dout.download(np.empty((n, Hp, Wp, 3), np.int32))
-    din.free()
-    dout.free()
-    return res[0] if single else res
+    return round_trip(f, np.asarray(rgb).ndim == 3,
+                      _k32("vcf_dct_dz_encode_k32", n * Hp * Wp * 3 * 4, n, H, W, block_size, Q, flags),
+                      (Hp, Wp, 3), np.int32)
 
 
 def decode_k32(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, block_size: int = 8) -> np.ndarray:
@@ -155,13 +127,8 @@ def decode_k32(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, block
     Hp, Wp = padded_shape(H, W, block_size)
     if f.shape[1:] != (Hp, Wp, 3):
         raise ValueError(f"index frames {f.shape[1:]} do not match {(Hp, Wp, 3)} for {H}x{W}")
-    din = DeviceBuffer.from_array(f)
-    dout = DeviceBuffer(n * H * W * 3)
-    call("vcf_dct_dz_decode_k32", din.ptr, n, H, W, block_size, int(Q), flags, dout.ptr, None)
-    res = dout.download(np.empty((n, H, W, 3), np.uint8))
-    din.free()
-    dout.free()
-    return res[0] if single else res
+    return round_trip(f, single, _k32("vcf_dct_dz_decode_k32", n * H * W * 3, n, H, W, block_size, Q, flags),
+                      (H, W, 3))
 
 
 def raw_encode_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, flags: int = 0,
@@ -169,12 +136,8 @@ def raw_encode_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, flags: i
     """encode_fn up to the quantizer for -a other than deadzone (offset 0, 2D-DCT.py:106-109):
     u8 RGB frames -> float32 HpxWpx3 coefficient frames (subband layout unless -x, -p applied)."""
     Hp, Wp = padded_shape(H, W, block_size)
-    if rgb.nbytes < n_frames * H * W * 3:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * Hp * Wp * 3 * 4)
-    elif out.nbytes < n_frames * Hp * Wp * 3 * 4:
-        raise ValueError("output buffer too small")
+    check_input(rgb, n_frames * H * W * 3)
+    out = output(out, n_frames * Hp * Wp * 3 * 4)
     call("vcf_dct_raw_encode", rgb.ptr, n_frames, H, W, block_size, flags, out.ptr, _h(stream))
     return out
 
@@ -183,11 +146,7 @@ def raw_decode_device(coef: DeviceBuffer, n_frames: int, H: int, W: int, flags: 
                       out: DeviceBuffer | None = None, stream=None, block_size: int = 8) -> DeviceBuffer:
     """decode_fn after another quantizer's dequantize_decom: int16 HpxWpx3 coefficient frames -> u8 RGB."""
     Hp, Wp = padded_shape(H, W, block_size)
-    if coef.nbytes < n_frames * Hp * Wp * 3 * 2:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * H * W * 3)
-    elif out.nbytes < n_frames * H * W * 3:
-        raise ValueError("output buffer too small")
+    check_input(coef, n_frames * Hp * Wp * 3 * 2)
+    out = output(out, n_frames * H * W * 3)
     call("vcf_dct_raw_decode", coef.ptr, n_frames, H, W, block_size, flags, out.ptr, _h(stream))
     return out

@@ -15,8 +15,8 @@ import struct
 
 import numpy as np
 
+from ._blockio import check_input, flags_from, frames_u8, output, round_trip
 from ._lib import VCF_DCT_NO_SUBBANDS, call
-from .dct import _frames, flags_from
 from .device import DeviceBuffer, _h
 
 __all__ = ["padded_shape", "check_blocks", "shape_bin", "flags_from", "moments_device", "encode_device", "decode_device",
@@ -49,12 +49,9 @@ def moments_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, block_size:
                    s1: DeviceBuffer | None = None, s2: DeviceBuffer | None = None, stream=None):
     """Frames in HBM -> (S1, S2) in HBM: int64 n x 3 x D and n x 3 x D x D (asynchronous on `stream`)."""
     D = block_size * block_size
-    if rgb.nbytes < n_frames * H * W * 3:
-        raise ValueError("input buffer too small")
-    s1 = DeviceBuffer(n_frames * 3 * D * 8) if s1 is None else s1
-    s2 = DeviceBuffer(n_frames * 3 * D * D * 8) if s2 is None else s2
-    if s1.nbytes < n_frames * 3 * D * 8 or s2.nbytes < n_frames * 3 * D * D * 8:
-        raise ValueError("output buffer too small")
+    check_input(rgb, n_frames * H * W * 3)
+    s1 = output(s1, n_frames * 3 * D * 8)
+    s2 = output(s2, n_frames * 3 * D * D * 8)
     call("vcf_klt_moments", rgb.ptr, n_frames, H, W, block_size, s1.ptr, s2.ptr, _h(stream))
     return s1, s2
 
@@ -64,12 +61,9 @@ def encode_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, weights: Dev
     """Frames and float64 weights (n x 3 x D x D) in HBM -> coefficient frames in HBM."""
     Hp, Wp = padded_shape(H, W, block_size)[:2]
     D = block_size * block_size
-    if rgb.nbytes < n_frames * H * W * 3 or weights.nbytes < n_frames * 3 * D * D * 8:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * Hp * Wp * 3)
-    elif out.nbytes < n_frames * Hp * Wp * 3:
-        raise ValueError("output buffer too small")
+    check_input(rgb, n_frames * H * W * 3)
+    check_input(weights, n_frames * 3 * D * D * 8)
+    out = output(out, n_frames * Hp * Wp * 3)
     call("vcf_klt_dz_encode", rgb.ptr, n_frames, H, W, block_size, int(Q), flags, weights.ptr, out.ptr, _h(stream))
     return out
 
@@ -79,12 +73,9 @@ def decode_device(k: DeviceBuffer, n_frames: int, H: int, W: int, weights: Devic
     """Coefficient frames and float32 weights (n x 3 x D x D) in HBM -> RGB frames in HBM."""
     Hp, Wp = padded_shape(H, W, block_size)[:2]
     D = block_size * block_size
-    if k.nbytes < n_frames * Hp * Wp * 3 or weights.nbytes < n_frames * 3 * D * D * 4:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * H * W * 3)
-    elif out.nbytes < n_frames * H * W * 3:
-        raise ValueError("output buffer too small")
+    check_input(k, n_frames * Hp * Wp * 3)
+    check_input(weights, n_frames * 3 * D * D * 4)
+    out = output(out, n_frames * H * W * 3)
     call("vcf_klt_dz_decode", k.ptr, n_frames, H, W, block_size, int(Q), flags, weights.ptr, out.ptr, _h(stream))
     return out
 
@@ -103,7 +94,7 @@ def moments(frames: np.ndarray, B: int = 8):
     """HxWx3 (or NxHxWx3) u8 -> (S1 int64 (3, D), S2 int64 (3, D, D)) (or with a leading N): the
     sums over the frame's padded blocks of s = 4 x and s s^T, exact."""
     single = np.asarray(frames).ndim == 3
-    f = _frames(frames, "rgb")
+    f = frames_u8(frames, "rgb")
     n, H, W, _ = f.shape
     check_blocks(H, W, B)
     din = DeviceBuffer.from_array(f)
@@ -134,7 +125,7 @@ def _train(din: DeviceBuffer, n: int, H: int, W: int, B: int) -> np.ndarray:
 def train(frames: np.ndarray, B: int = 8) -> np.ndarray:
     """The learned bases, float64 (3, D, D) (or (N, 3, D, D)): moments on the GPU, eigh on the host."""
     single = np.asarray(frames).ndim == 3
-    f = _frames(frames, "rgb")
+    f = frames_u8(frames, "rgb")
     n, H, W, _ = f.shape
     check_blocks(H, W, B)
     din = DeviceBuffer.from_array(f)
@@ -159,21 +150,19 @@ def encode(frames: np.ndarray, Q: int = 32, flags: int = 0, B: int = 8, weights:
     """Host convenience: HxWx3 (or NxHxWx3) u8 -> (HpxWpx3 u8 indices, float64 weights).  The basis is
     trained per frame when `weights` (float64 (3, D, D), or one per frame) is not given."""
     single = np.asarray(frames).ndim == 3
-    f = _frames(frames, "rgb")
+    f = frames_u8(frames, "rgb")
     n, H, W, _ = f.shape
     check_blocks(H, W, B)
-    Hp, Wp = padded_shape(H, W, B)[:2]
-    din = DeviceBuffer.from_array(f)
-    try:
+    w = None
+
+    def launch(din):
+        nonlocal w
         w = _train(din, n, H, W, B) if weights is None else _weights(weights, n, B, np.float64)
         dw = DeviceBuffer.from_array(w)
-        dout = encode_device(din, n, H, W, dw, Q, flags, block_size=B)
-        res = dout.download(np.empty((n, Hp, Wp, 3), np.uint8))
-        dw.free()
-        dout.free()
-    finally:
-        din.free()
-    return (res[0], w[0]) if single else (res, w)
+        return encode_device(din, n, H, W, dw, Q, flags, block_size=B), dw
+
+    res = round_trip(f, single, launch, padded_shape(H, W, B)[:2] + (3,))
+    return res, (w[0] if single else w)
 
 
 def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, B: int = 8,
@@ -182,19 +171,12 @@ def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, B: int = 
     {out}_weights.npz -> HxWx3 u8 reconstruction."""
     if weights32 is None:
         raise ValueError("decode needs the float32 weights the encoder stored")
-    single = np.asarray(k).ndim == 3
-    f = _frames(k, "k")
+    f = frames_u8(k, "k")
     n = f.shape[0]
     check_blocks(H, W, B)
     Hp, Wp = padded_shape(H, W, B)[:2]
     if f.shape[1:3] != (Hp, Wp):
         raise ValueError(f"index frames {f.shape[1:3]} do not match {(Hp, Wp)} for {H}x{W}")
-    w = _weights(weights32, n, B, np.float32)
-    din = DeviceBuffer.from_array(f)
-    dw = DeviceBuffer.from_array(w)
-    dout = decode_device(din, n, H, W, dw, Q, flags, block_size=B)
-    res = dout.download(np.empty((n, H, W, 3), np.uint8))
-    din.free()
-    dw.free()
-    dout.free()
-    return res[0] if single else res
+    return round_trip(f, np.asarray(k).ndim == 3,
+                      lambda din, dw: decode_device(din, n, H, W, dw, Q, flags, block_size=B), (H, W, 3),
+                      extra=[_weights(weights32, n, B, np.float32)])

@@ -13,8 +13,8 @@ import struct
 
 import numpy as np
 
+from ._blockio import check_input, flags_from, frames_u8, output, round_trip
 from ._lib import VCF_DCT_NO_SUBBANDS, VCF_DCT_PERCEPTUAL, call
-from .dct import _frames, flags_from
 from .device import DeviceBuffer, _h
 
 __all__ = ["padded_shape", "shape_bin", "flags_from", "encode_device", "decode_device", "encode", "decode",
@@ -38,12 +38,8 @@ def encode_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, Q: int = 32,
                   out: DeviceBuffer | None = None, stream=None, block_size: int = 8) -> DeviceBuffer:
     """Frames resident in HBM -> coefficient frames in HBM (asynchronous on `stream`)."""
     Hp, Wp = padded_shape(H, W, block_size)[:2]
-    if rgb.nbytes < n_frames * H * W * 3:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * Hp * Wp * 3)
-    elif out.nbytes < n_frames * Hp * Wp * 3:
-        raise ValueError("output buffer too small")
+    check_input(rgb, n_frames * H * W * 3)
+    out = output(out, n_frames * Hp * Wp * 3)
     call("vcf_mdct_dz_encode", rgb.ptr, n_frames, H, W, block_size, int(Q), flags, out.ptr, _h(stream))
     return out
 
@@ -51,41 +47,26 @@ def encode_device(rgb: DeviceBuffer, n_frames: int, H: int, W: int, Q: int = 32,
 def decode_device(k: DeviceBuffer, n_frames: int, H: int, W: int, Q: int = 32, flags: int = 0,
                   out: DeviceBuffer | None = None, stream=None, block_size: int = 8) -> DeviceBuffer:
     Hp, Wp = padded_shape(H, W, block_size)[:2]
-    if k.nbytes < n_frames * Hp * Wp * 3:
-        raise ValueError("input buffer too small")
-    if out is None:
-        out = DeviceBuffer(n_frames * H * W * 3)
-    elif out.nbytes < n_frames * H * W * 3:
-        raise ValueError("output buffer too small")
+    check_input(k, n_frames * Hp * Wp * 3)
+    out = output(out, n_frames * H * W * 3)
     call("vcf_mdct_dz_decode", k.ptr, n_frames, H, W, block_size, int(Q), flags, out.ptr, _h(stream))
     return out
 
 
 def encode(rgb: np.ndarray, Q: int = 32, flags: int = 0, block_size: int = 8) -> np.ndarray:
     """Host convenience: HxWx3 (or NxHxWx3) u8 -> HpxWpx3 (NxHpxWpx3) u8 indices."""
-    single = np.asarray(rgb).ndim == 3
-    f = _frames(rgb, "rgb")
+    f = frames_u8(rgb, "rgb")
     n, H, W, _ = f.shape
-    Hp, Wp = padded_shape(H, W, block_size)[:2]
-    din = DeviceBuffer.from_array(f)
-    dout = encode_device(din, n, H, W, Q, flags, block_size=block_size)
-    res = dout.download(np.empty((n, Hp, Wp, 3), np.uint8))
-    din.free()
-    dout.free()
-    return res[0] if single else res
+    return round_trip(f, np.asarray(rgb).ndim == 3,
+                      lambda din: encode_device(din, n, H, W, Q, flags, block_size=block_size),
+                      padded_shape(H, W, block_size)[:2] + (3,))
 
 
 def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, block_size: int = 8) -> np.ndarray:
     """Host convenience: HpxWpx3 (or N...) u8 indices -> HxWx3 u8 reconstruction."""
-    single = np.asarray(k).ndim == 3
-    f = _frames(k, "k")
-    n = f.shape[0]
+    f = frames_u8(k, "k")
     Hp, Wp = padded_shape(H, W, block_size)[:2]
     if f.shape[1:3] != (Hp, Wp):
         raise ValueError(f"index frames {f.shape[1:3]} do not match {(Hp, Wp)} for {H}x{W}")
-    din = DeviceBuffer.from_array(f)
-    dout = decode_device(din, n, H, W, Q, flags, block_size=block_size)
-    res = dout.download(np.empty((n, H, W, 3), np.uint8))
-    din.free()
-    dout.free()
-    return res[0] if single else res
+    return round_trip(f, np.asarray(k).ndim == 3,
+                      lambda din: decode_device(din, len(f), H, W, Q, flags, block_size=block_size), (H, W, 3))
