@@ -616,6 +616,90 @@ int vcf_lm_encode(const void *x_dev, int32_t x_dtype, int64_t n_px, int32_t chan
 int vcf_lm_decode(const void *k_dev, int32_t k_dtype, int64_t n_px, int32_t channels, const double *centroids_dev,
                   int32_t n_levels, void *y_dev, int32_t y_dtype, int32_t *bad_dev, void *stream);
 
+/* ---- vector quantization (src/VQ.py, src/color-VQ.py) ---------------------------
+ * k-means as sklearn.cluster.KMeans(algorithm="lloyd", n_init=1) runs it, on the
+ * blocks of one u8 frame of H x W x C samples, 1 <= C <= 4.  The block size BS
+ * is 1..16 and divides H and W (else VCF_ERR_INVALID: the reference's reshape
+ * raises there).  Vector n is block (n / (W/BS), n % (W/BS)) in raster order,
+ * img[y:y+BS, x:x+BS, :] flattened row-major (channel fastest): D = BS*BS*C
+ * values, N = (H/BS)*(W/BS) vectors.  1 <= K <= min(N, 4096); labels are
+ * uint16, centroids K x D float64 (row-major).  Every argument is checked
+ * before any device work; the work is enqueued on `stream`.  vcf_vq_init_pp and
+ * vcf_vq_fit run host-driven loops: they synchronise `stream` and have finished
+ * when they return; the other three only enqueue.
+ *
+ * vcf_vq_assign: labels[n] = argmin_j dist(n, j), the lowest j on a tie (strict
+ * `<` while j ascends), and, when dist_dev is not NULL, that least distance.
+ * The arithmetic is the direct difference form in float64,
+ *     dist = 0;  for d = 0 .. D-1:  t = x_d - c_jd;  dist = dist + t * t;
+ * with x_d converted exactly and three separate roundings per term (subtract,
+ * multiply, add: no FMA, the library is built with -ffp-contract=off), on the
+ * vector ALU.  numpy restates it bit for bit, ties included.  The centroids
+ * pass through LDS in tiles of KT centroids (KT * D * 8 bytes <= 32 KiB, at
+ * least 8 centroids, so at most 64 KiB when D = 1024); tiling changes no
+ * result, each distance is one chain over d. */
+int vcf_vq_assign(const uint8_t *img_dev, int32_t H, int32_t W, int32_t C, int32_t block_size,
+                  const double *centroids_dev, int32_t K, uint16_t *labels_dev, double *dist_dev, void *stream);
+/* sums[j][d] = sum of x_d over the vectors labelled j, counts[j] = their number:
+ * int64, zeroed here, integer arithmetic throughout (the result depends on no
+ * order, tiling or atomic).  A vector whose label is >= K is left out. */
+int vcf_vq_accumulate(const uint8_t *img_dev, int32_t H, int32_t W, int32_t C, int32_t block_size,
+                      const uint16_t *labels_dev, int32_t K, int64_t *sums_dev, int64_t *counts_dev, void *stream);
+/* Greedy k-means++ (sklearn's _kmeans_plusplus) in exact integers.  Candidates
+ * are data vectors, so every squared distance and potential is an int64.
+ *     u(step, trial) = mix(seed + 0x9E3779B97F4A7C15 * (16 * step + trial + 1))   (mod 2^64)
+ *     mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *             return z ^ (z >> 31)                       (splitmix64's output function)
+ *     mulhi64(a, b) = (a * b) >> 64
+ *   step 0: id_0 = mulhi64(u(0, 0), N);  closest[n] = |x_n - x_id0|^2
+ *   step c = 1 .. K-1, with T = 2 + floor(ln K) trials:
+ *     pot = sum(closest);  r_t = mulhi64(u(c, t), pot);
+ *     candidate_t = the first index whose running sum closest[0] + ... + closest[i]
+ *                   exceeds r_t  (vector 0 when pot = 0);
+ *     pot_t = sum_n min(closest[n], |x_n - x_candidate_t|^2);
+ *     id_c = the candidate of least pot_t (the lowest t on a tie);
+ *     closest[n] = min(closest[n], |x_n - x_id_c|^2)
+ * centroids[c] = x_id_c.  ids_host (host memory, K int64, may be NULL) receives
+ * the chosen indices.  Per step only T candidate indices and the partial sums of
+ * 256-vector chunks cross to the host; being integers, no launch geometry
+ * changes a result. */
+int vcf_vq_init_pp(const uint8_t *img_dev, int32_t H, int32_t W, int32_t C, int32_t block_size, int32_t K,
+                   uint64_t seed, double *centroids_dev, int64_t *ids_host, void *stream);
+/* The host-side report of vcf_vq_fit. */
+#define VCF_VQ_STOP_STRICT 0   /* the labels did not change */
+#define VCF_VQ_STOP_TOL 1      /* the summed squared centre shift fell to tol_abs or under */
+#define VCF_VQ_STOP_MAX_ITER 2
+typedef struct vcf_vq_report {
+    int32_t n_iter;
+    int32_t stop_reason;
+    int64_t relocations;   /* vectors handed to empty clusters, over all iterations */
+    double inertia;        /* sum over n, in index order, of dist(n, labels[n]) to the returned centroids */
+    double tol_abs;        /* tol * mean_d((N * S2_d - S1_d^2) / N^2), exact integer moments, one division per d */
+} vcf_vq_report;
+/* Lloyd's iteration with sklearn's semantics (_kmeans_single_lloyd), started
+ * from init_centroids_dev (K x D float64; it may be centroids_dev itself) or,
+ * when that is NULL, from vcf_vq_init_pp(seed).  Per iteration: assign,
+ * accumulate, centroid = (double)sum / (double)count (one division).  An empty
+ * cluster takes the vector farthest from its own centroid (largest distance,
+ * the lowest index on a tie, successive empty clusters in ascending order the
+ * next farthest); the vector leaves its old cluster's sum and count; the labels
+ * of that iteration stay.  When the farthest distance left is 0 the cluster
+ * stays empty, and a cluster without members keeps its centroid.  The loop ends
+ * when the labels equal the previous iteration's (strict), else when the sum
+ * over all j, d of (new - old)^2 is <= tol_abs, else after max_iter (>= 1)
+ * iterations; unless strict, one more assign makes the labels match the
+ * returned centroids.  *report is host memory. */
+int vcf_vq_fit(const uint8_t *img_dev, int32_t H, int32_t W, int32_t C, int32_t block_size, int32_t K, uint64_t seed,
+               int32_t max_iter, double tol, const double *init_centroids_dev, double *centroids_dev,
+               uint16_t *labels_dev, vcf_vq_report *report, void *stream);
+/* labels (Hl x Wl) and centroids -> the u8 image (Hl*BS x Wl*BS x C): each
+ * sample is the centroid value truncated into int16 and then its low byte
+ * (VQ.py:125-137 and .astype(np.uint8); values outside int32 saturate first).
+ * A label >= K sets *bad_dev to 1 (the caller zeroes it; numpy's IndexError)
+ * and writes 0; nothing is read out of bounds. */
+int vcf_vq_decode(const uint16_t *labels_dev, int32_t Hl, int32_t Wl, int32_t C, int32_t block_size,
+                  const double *centroids_dev, int32_t K, uint8_t *img_dev, int32_t *bad_dev, void *stream);
+
 /* ---- cross-rank exchange on RCCL over xGMI -------------------
  * Frames shard across one process per GPU with no collective on the data
  * path; the one exchange step of the III / IPP drivers is after coding: an

@@ -116,6 +116,11 @@ SIGNATURES = {
     "vcf_lm_design": [_P, _I32, _I32, _I32, _P],
     "vcf_lm_encode": [_P, _I32, _I64, _I32, _P, _I32, _P, _I32, _P],
     "vcf_lm_decode": [_P, _I32, _I64, _I32, _P, _I32, _P, _I32, _P, _P],
+    "vcf_vq_assign": [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P],
+    "vcf_vq_accumulate": [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P],
+    "vcf_vq_init_pp": [_P, _I32, _I32, _I32, _I32, _I32, ctypes.c_uint64, _P, _P, _P],
+    "vcf_vq_fit": [_P, _I32, _I32, _I32, _I32, _I32, ctypes.c_uint64, _I32, ctypes.c_double, _P, _P, _P, _P, _P],
+    "vcf_vq_decode": [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P],
     "vcf_wavelet_index": [ctypes.c_char_p, _PI32],
     "vcf_dwt_layout": [_I32, _I32, _I32, _PI32, _PI32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
     "vcf_dwt_dz_encode": [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],

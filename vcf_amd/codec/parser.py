@@ -328,6 +328,55 @@ def deadzone_parser(description: str = "Image quantization using a deadzone scal
     return p
 
 
+DEFAULT_BLOCK_SIZE_VQ = 4               # VQ.py:15
+DEFAULT_N_CLUSTERS = 256                # VQ.py:17
+DEFAULT_N_COLOR_CLUSTERS = 32           # color-VQ.py:14
+
+
+def add_vq(enc, dec):
+    """VQ.py:20-24 (-f on decode only; no seed flag: the reference has none)."""
+    enc.add_argument("-b", "--block_size_VQ", type=int_or_str,
+                     help=f"Block size (default: {DEFAULT_BLOCK_SIZE_VQ}). The block size must be a multiple of "
+                          "the image size.", default=DEFAULT_BLOCK_SIZE_VQ)
+    dec.add_argument("-b", "--block_size_VQ", type=int_or_str,
+                     help=f"Block size (default: {DEFAULT_BLOCK_SIZE_VQ})", default=DEFAULT_BLOCK_SIZE_VQ)
+    for p in (enc, dec):
+        p.add_argument("-q", "--N_clusters", type=int_or_str,
+                       help=f"Number of clusters (default: {DEFAULT_N_CLUSTERS})", default=DEFAULT_N_CLUSTERS)
+    dec.add_argument("-f", "--filter", type=int_or_str,
+                     help=f"Denoising filter (default: {DEFAULT_FILTER})", default=DEFAULT_FILTER)
+
+
+def add_color_vq(enc, dec):
+    """color-VQ.py:17-19."""
+    for p in (enc, dec):
+        p.add_argument("-q", "--N_color_clusters", type=int_or_str,
+                       help=f"Number of clusters (default: {DEFAULT_N_COLOR_CLUSTERS})",
+                       default=DEFAULT_N_COLOR_CLUSTERS)
+    dec.add_argument("-f", "--filter", type=int_or_str,
+                     help=f"Denoising filter (default: {DEFAULT_FILTER})", default=DEFAULT_FILTER)
+
+
+def build_vq_parser(description: str = "Image (spatial 2D) quantization using a vector quantizer.",
+                    entropy: str = DEFAULT_EIC):
+    """`python VQ.py ...` (VQ.py -> no_filter.py -> TIFF.py)."""
+    p, enc, dec = base_parser(description)
+    add_vq(enc, dec)
+    add_filter(enc, dec, entropy)
+    add_eic(enc, dec)
+    return p
+
+
+def build_color_vq_parser(description: str = "Color quantization using Vector Quantization (VQ).",
+                          entropy: str = DEFAULT_EIC):
+    """`python color-VQ.py ...` (color-VQ.py -> no_filter.py -> TIFF.py)."""
+    p, enc, dec = base_parser(description)
+    add_color_vq(enc, dec)
+    add_filter(enc, dec, entropy)
+    add_eic(enc, dec)
+    return p
+
+
 def tiff_parser(description: str = "Entropy Encoding of images using TIFF (Tag Image File Format). "):
     """`python TIFF.py ...` (TIFF.py -> entropy_image_coding.py)."""
     p, enc, dec = base_parser(description)
