@@ -187,6 +187,52 @@ int vcf_klt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
 int vcf_klt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const float *weights_f32_dev, uint8_t *rgb_dev, void *stream);
 
+/* ---- 2D-LBT (2D-LBT.py) --------------------------------------------------
+ * A linear autoencoder of the B x B blocks (D = B * B), trained per frame with
+ * Adam on mean((x^ - x)^2) + lambda mean_j log(var_j(y) + 1e-6); the rows are
+ * the blocks of all three YCoCg channels minus one scalar mean.  The model is
+ * linear, so the training reads the frame once (the moments) and then works
+ * on D x D matrices.  2 <= block_size <= 8 (else VCF_ERR_UNSUPPORTED);
+ * arguments are checked before any device work; work is enqueued on the
+ * caller's stream.  The padded shape is vcf_klt_padded_shape's. */
+
+/* Per frame, pooled over the three channels: s1_dev (n_frames x D float64) =
+ * sum of x, s2_dev (n_frames x D x D float64, full symmetric) = sum of x x^T
+ * over the 3 N blocks, x = the YCoCg values after the zero pad and -128.
+ * Every partial sum is an integer multiple of 1/16 below 2^53: exact, in any
+ * order.  Each frame is read once; no float copy of it is written. */
+int vcf_lbt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
+                    double *s1_dev, double *s2_dev, void *stream);
+
+/* 2D-LBT.py:94-128 from the moments: `epochs` steps of torch.optim.Adam
+ * (defaults; learning rate lr) over both matrices, all in one launch, one
+ * workgroup per frame.  rows = 3 N, the number of blocks the moments were
+ * summed over.  we_dev / wd_dev: n_frames x D x D float32, the initial weights
+ * in, the trained ones out (nn.Linear layout: y = We x, x^ = Wd y).  mean_dev:
+ * n_frames float32, the scalar mean.  loss_dev: n_frames x 3 float32: the
+ * loss at the final weights, its MSE term and mean_j log(var_j + 1e-6).
+ * float32 products on the matrix cores, inner index ascending. */
+int vcf_lbt_train(const double *s1_dev, const double *s2_dev, int64_t n_frames, int32_t block_size, int64_t rows,
+                  int32_t epochs, double lr, double lambda, float *we_dev, float *wd_dev, float *mean_dev,
+                  float *loss_dev, void *stream);
+
+/* 2D-LBT.py encode_fn :364-452 with the encoder matrix given: zero pad, -128,
+ * YCoCg, x - mean (float32), y[k] = sum_j We[k][j] x[j] (float32 FMAs, j
+ * ascending), with VCF_DCT_PERCEPTUAL * (QSSs / 121 or 99) as a float64
+ * product rounded to float32, / Q (float32), truncated, +128, clipped to
+ * 0..255; subband layout unless VCF_DCT_NO_SUBBANDS.  we_dev: n_frames x D x D,
+ * mean_dev: n_frames.  k_dev: n_frames x Hp x Wp x 3. */
+int vcf_lbt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
+                      uint32_t flags, const float *we_dev, const float *mean_dev, uint8_t *k_dev, void *stream);
+
+/* The inverse, 2D-LBT.py decode_fn :476-563 with the stored decoder matrix as
+ * it is: Q (k - 128) in int16 (with VCF_DCT_PERCEPTUAL divided by the weight
+ * in float64 and truncated back into int16), x[j] = sum_k Wd[j][k] y[k]
+ * (float32 FMAs, k ascending), + mean, crop, inverse YCoCg and +128 in
+ * float32, clip, truncate. */
+int vcf_lbt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
+                      uint32_t flags, const float *wd_dev, const float *mean_dev, uint8_t *rgb_dev, void *stream);
+
 /* 1 if block_size has a HIP transform: every 1 <= B <= 4096 -- compiled
  * kernels for the 38 5-smooth B <= 128 (every -L candidate 2, 4, ..., 128,
  * 2D-DCT.py:536), run-time-length kernels for the rest: rfftp plans with the

@@ -28,10 +28,31 @@ def _tcbaac_prior(args=None):
                            nclass=PRIOR_CLASSES)
 
 
+class ZlibCodec:
+    """z_lib.py:12-29: the index array as np.savez_compressed(a=...), on the host."""
+    file_extension = ".npz"
+
+    def compress(self, img):
+        import io
+
+        import numpy as np
+        out = io.BytesIO()
+        np.savez_compressed(file=out, a=img)
+        return out
+
+    def decompress(self, codestream):
+        import io
+
+        import numpy as np
+        data = codestream.read() if hasattr(codestream, "read") else codestream
+        with np.load(io.BytesIO(data)) as z:
+            return z["a"]
+
+
 # TCBAAC: CBAAC in independent segments on the GPU (vcf_amd/tcbaac.py, a new container);
 # TCBAACP: the same with every segment's models seeded by a prior row of the frame: 8 rows, one per run of
 # segments (about one subband row each), 4096-symbol segments (container version 3)
-ENTROPY_CODECS = {"TIFF": TIFFCodec, "CBAAC": _cbaac, "CBAHC": _cbahc, "TCBAAC": _tcbaac, "TCBAACP": _tcbaac_prior}
+ENTROPY_CODECS = {"TIFF": TIFFCodec, "z_lib": ZlibCodec, "CBAAC": _cbaac, "CBAHC": _cbahc, "TCBAAC": _tcbaac, "TCBAACP": _tcbaac_prior}
 
 
 def register_entropy_codec(name, cls):

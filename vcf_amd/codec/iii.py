@@ -44,7 +44,10 @@ def transform_codec(args):
     if name == "2D-KLT":
         from .klt2d import CoDec
         return CoDec(args)
-    raise NotImplementedError(f"transform {name!r}: 2D-DCT, 2D-DWT, 2D-MDCT and 2D-KLT are on the HIP path")
+    if name == "2D-LBT":
+        from .lbt2d import CoDec
+        return CoDec(args)
+    raise NotImplementedError(f"transform {name!r}: 2D-DCT, 2D-DWT, 2D-MDCT, 2D-KLT and 2D-LBT are on the HIP path")
 
 
 def _frame_inputs(original: str, n: int):

@@ -202,6 +202,35 @@ def add_klt(enc, dec):
                        default=False)
 
 
+def add_lbt(enc, dec):
+    """2D-LBT.py:38-51 (-L is the weight of the log-variance term here and starts no block-size
+    search; its help text is the reference's)."""
+    enc.add_argument("-B", "--block_size_DCT", type=int_or_str,
+                     help=f"Block size (default: {DEFAULT_BLOCK_SIZE})", default=DEFAULT_BLOCK_SIZE)
+    enc.add_argument("--side_info", type=str, help="Ruta para guardar los pesos entrenados (opcional)", default=None)
+    enc.add_argument("--epochs", type=int, help="Number of training epochs (default: %(default)s)", default=1000)
+    enc.add_argument("--lr", type=float, help="Learning rate (default: %(default)s)", default=1e-3)
+    enc.add_argument("-t", "--color_transform", type=int_or_str,
+                     help=f"Color transform (default: \"{DEFAULT_CT}\")", default=DEFAULT_CT)
+    enc.add_argument("-p", "--perceptual_quantization", action="store_true",
+                     help="Use perceptual quantization (default: \"False\")", default=False)
+    enc.add_argument("-L", "--Lambda", type=int_or_str,
+                     help="Relative weight between the rate and the distortion. If provided (float), the block "
+                          "size is RD-optimized between {2**i; i=1,2,3,4,5,6,7}. For example, if Lambda=1.0, "
+                          "then the rate and the distortion have the same weight. (default: 1e-6)", default=None)
+    enc.add_argument("-x", "--disable_subbands", action="store_true",
+                     help="Disable the coefficients reordering in subbands (default: \"False\")", default=False)
+    dec.add_argument("-B", "--block_size_DCT", type=int_or_str,
+                     help=f"Block size (default: {DEFAULT_BLOCK_SIZE})", default=DEFAULT_BLOCK_SIZE)
+    dec.add_argument("--side_info", type=str, help="Ruta para cargar los pesos entrenados (opcional)", default=None)
+    dec.add_argument("-t", "--color_transform", type=int_or_str,
+                     help=f"Color transform (default: \"{DEFAULT_CT}\")", default=DEFAULT_CT)
+    dec.add_argument("-p", "--perceptual_quantization", action="store_true",
+                     help="Use perceptual dequantization (default: \"False\")", default=False)
+    dec.add_argument("-x", "--disable_subbands", action="store_true",
+                     help="Disable the coefficients reordering in subbands (default: \"False\")", default=False)
+
+
 def add_dwt(enc, dec):
     """2D-DWT.py:25-31."""
     for p in (enc, dec):
@@ -259,6 +288,19 @@ def klt_parser(description: str = "Exploiting spatial redundancy with a learned 
     return p
 
 
+def lbt_parser(description: str = "Exploiting spatial redundancy with the 2D Discrete Cosine Transform of "
+                                  "constant block size.", entropy: str = DEFAULT_EIC):
+    """`python 2D-LBT.py ...` (2D-LBT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py); the
+    description is the reference's own docstring."""
+    p, enc, dec = base_parser(description)
+    add_lbt(enc, dec)
+    add_ycocg(enc, dec)
+    add_deadzone(enc, dec)
+    add_filter(enc, dec, entropy)
+    add_eic(enc, dec)
+    return p
+
+
 def dwt_parser(description: str = "Exploiting spatial redundancy with the 2D dyadic Discrete Wavelet "
                                   "Transform.", entropy: str = DEFAULT_EIC):
     """`python 2D-DWT.py ...` (2D-DWT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py)."""
@@ -282,6 +324,8 @@ def iii_parser(description: str = "III coding: runs a 2D image codec for each im
         add_mdct(enc, dec)
     elif transform == "2D-KLT":
         add_klt(enc, dec)
+    elif transform == "2D-LBT":
+        add_lbt(enc, dec)
     else:
         add_dct(enc, dec)
     add_ycocg(enc, dec)
