@@ -505,6 +505,54 @@ int vcf_cbaac_encode_prior(const uint8_t *symbols, int64_t n, int32_t order, con
 int vcf_cbaac_decode_prior(const uint8_t *bytes, int64_t nbytes, int64_t n, int32_t order, const uint16_t *prior,
                            uint8_t *symbols_out);
 
+/* ---- tiled CBAAC with a two-dimensional context (container version 4; not in
+ * the reference) ----------------------------------------------------------------
+ * A (H, W, C) u8 frame is coded plane by plane in th x tw tiles (edge tiles
+ * cropped; tile t = (c ty + r) tx + q for tile row r, tile column q of plane
+ * c, ty x tx tiles per plane).  A tile's symbols go in raster order through
+ * the A8 coder, flushed at the tile's end, each through one of 16
+ * AdaptiveModels (CBAAC.py:17-47): ctx = 4 q(|left - 128|) + q(|up - 128|),
+ * q(v) = min(v, 3), a neighbour outside the tile counting as 0.  Tile t of a
+ * plane's ty tx takes prior class floor(t_in_plane nclass / (ty tx)); the
+ * tile's 16 models start from the class's 16 rows, row (class, ctx) = 1 +
+ * floor(hist[s] * 8192 / n) over the class's symbols in that context (all
+ * ones where there are none).  priors = nclass x 16 x 256 uint16.
+ *
+ * Host (one frame; the yardstick of the GPU coder and the CPU path): */
+int64_t vcf_cbaac2d_tiles(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw);
+int vcf_cbaac2d_prior(const uint8_t *sym, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw, int32_t nclass,
+                      uint16_t *priors);
+/* tiles back to back in out; tile_bytes (tiles int64) their sizes */
+int vcf_cbaac2d_encode(const uint8_t *sym, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw, int32_t nclass,
+                       const uint16_t *priors, uint8_t *out, int64_t out_capacity, int64_t *tile_bytes,
+                       int64_t *out_bytes);
+/* tile t's bytes are bytes[tile_offsets[t] .. tile_offsets[t+1]) */
+int vcf_cbaac2d_decode(const uint8_t *bytes, const int64_t *tile_offsets, int64_t H, int64_t W, int64_t C, int64_t th,
+                       int64_t tw, int32_t nclass, const uint16_t *priors, uint8_t *sym_out);
+/* GPU, batches of n_frames (<= 65535) frames, one wave per tile, th * tw <=
+ * 65536 and tw <= 256 (VCF_ERR_UNSUPPORTED above); every tile's bytes equal
+ * the host coder's.  Device pointers, the caller's stream.  Frame f's symbols
+ * at sym_dev + f * frame_stride; priors_dev = n_frames x nclass x 16 x 256
+ * uint16 (8-byte aligned), hist_dev = as many uint32 of scratch; frame f's
+ * packed tiles at out_dev + f * out_frame_capacity (vcf_cbaac_tiled2d_bound
+ * always suffices), its tile byte counts and their total at tile_bytes_dev +
+ * f * (tiles + 1); ws_dev = vcf_cbaac_tiled2d_workspace bytes.  Decode: frame
+ * f's tile offsets at tile_offsets_dev + f * (tiles + 1), offsets into
+ * in_dev; its symbols to sym_dev + f * out_frame_stride. */
+int64_t vcf_cbaac_tiled2d_tiles(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw);
+int64_t vcf_cbaac_tiled2d_workspace(int64_t n_frames, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw);
+int64_t vcf_cbaac_tiled2d_bound(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw);
+int vcf_cbaac_tiled2d_prior_frames(const uint8_t *sym_dev, int64_t n_frames, int64_t H, int64_t W, int64_t C,
+                                   int64_t frame_stride, int64_t th, int64_t tw, int32_t nclass, uint16_t *priors_dev,
+                                   uint32_t *hist_dev, void *stream);
+int vcf_cbaac_tiled2d_encode_frames(const uint8_t *sym_dev, int64_t n_frames, int64_t H, int64_t W, int64_t C,
+                                    int64_t frame_stride, const uint16_t *priors_dev, int32_t nclass, int64_t th,
+                                    int64_t tw, uint8_t *out_dev, int64_t out_frame_capacity, int64_t *tile_bytes_dev,
+                                    void *ws_dev, void *stream);
+int vcf_cbaac_tiled2d_decode_frames(const uint8_t *in_dev, const int64_t *tile_offsets_dev, int64_t n_frames, int64_t H,
+                                    int64_t W, int64_t C, const uint16_t *priors_dev, int32_t nclass, int64_t th,
+                                    int64_t tw, uint8_t *sym_dev, int64_t out_frame_stride, void *stream);
+
 /* ---- CBAHC entropy codec (CBAHC.py), host code --------------------------------- */
 
 /* Worst-case code-stream bytes for n symbols. */

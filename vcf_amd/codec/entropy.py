@@ -28,6 +28,11 @@ def _tcbaac_prior(args=None):
                            nclass=PRIOR_CLASSES)
 
 
+def _tcbaac_2d(args=None):
+    from ..tcbaac import PRIOR_CLASSES, TILE_2D, TiledCBAACCodec
+    return TiledCBAACCodec(0, prior=True, nclass=PRIOR_CLASSES, ctx2d=True, tile=TILE_2D)
+
+
 class ZlibCodec:
     """z_lib.py:12-29: the index array as np.savez_compressed(a=...), on the host."""
     file_extension = ".npz"
@@ -51,8 +56,11 @@ class ZlibCodec:
 
 # TCBAAC: CBAAC in independent segments on the GPU (vcf_amd/tcbaac.py, a new container);
 # TCBAACP: the same with every segment's models seeded by a prior row of the frame: 8 rows, one per run of
-# segments (about one subband row each), 4096-symbol segments (container version 3)
-ENTROPY_CODECS = {"TIFF": TIFFCodec, "z_lib": ZlibCodec, "CBAAC": _cbaac, "CBAHC": _cbahc, "TCBAAC": _tcbaac, "TCBAACP": _tcbaac_prior}
+# segments (about one subband row each), 4096-symbol segments (container version 3);
+# TCBAAC2D: every channel plane in 64 x 64 tiles, each symbol's model chosen by the magnitudes of its left and
+# upper neighbours in the tile (16 contexts), seeded per prior class and context (container version 4)
+ENTROPY_CODECS = {"TIFF": TIFFCodec, "z_lib": ZlibCodec, "CBAAC": _cbaac, "CBAHC": _cbahc, "TCBAAC": _tcbaac, "TCBAACP": _tcbaac_prior,
+                  "TCBAAC2D": _tcbaac_2d}
 
 
 def register_entropy_codec(name, cls):
@@ -65,4 +73,4 @@ def make_entropy(args):
     if ec_name not in ENTROPY_CODECS:
         raise NotImplementedError(f"entropy codec {ec_name!r} (have: {sorted(ENTROPY_CODECS)})")
     maker = ENTROPY_CODECS[ec_name]
-    return maker(args) if maker in (_cbaac, _cbahc, _tcbaac, _tcbaac_prior) else maker()
+    return maker(args) if maker in (_cbaac, _cbahc, _tcbaac, _tcbaac_prior, _tcbaac_2d) else maker()

@@ -10,8 +10,9 @@ chunk never leaves the GPU until its code-streams are final:
      (vcf_dct_dz_encode), indices stay in HBM;
   2. the GPU entropy stage, all frames in one launch per stage, only the
      small size tables coming to the host: either every frame's indices
-     coded as a prior-seeded tiled CBAAC stream (`-c TCBAACP`,
-     vcf_amd/tcbaac.py), or -- the reference's default `-c TIFF` -- every
+     coded as a prior-seeded tiled CBAAC stream (`-c TCBAACP`, or `-c
+     TCBAAC2D` with the two-dimensional context; vcf_amd/tcbaac.py), or --
+     the reference's default `-c TIFF` -- every
      TIFF strip of every frame deflated exactly as zlib would
      (vcf_amd/zlib_gpu.py);
   3. every frame's file (header + payload: exactly the bytes
@@ -55,8 +56,8 @@ class DeviceIII:
         self.n_sym = self.Hp * self.Wp * 3
         self.stream = Stream()
         self.k = DeviceBuffer(max(self.n_local * self.n_sym, 1))
-        if entropy not in ("TCBAACP", "TIFF"):
-            raise ValueError(f"entropy codec {entropy!r}: TCBAACP or TIFF")
+        if entropy not in ("TCBAACP", "TCBAAC2D", "TIFF"):
+            raise ValueError(f"entropy codec {entropy!r}: TCBAACP, TCBAAC2D or TIFF")
         self.entropy = entropy
         if entropy == "TIFF":
             self.batch = None
@@ -65,6 +66,8 @@ class DeviceIII:
             if not Z.covers(self.shape, 1):
                 raise NotImplementedError(f"{self.Wp}-pixel rows: TIFF strips of {self.strip_bytes} bytes are beyond "
                                           f"the GPU deflate's {Z.max_strip()}; use the file path (dct2d.encode_fns)")
+        elif entropy == "TCBAAC2D":
+            self.batch = T.FrameBatch2D(self.n_local, self.shape, T.TILE_2D, nclass)
         else:
             self.batch = T.FrameBatch(self.n_local, self.n_sym, 0, seg_len, prior=True, nclass=nclass)
         self.exchange = Exchange(comm, self.rank, self.world, self.N, lambda r: frame_range(self.N, r, self.world),

@@ -83,10 +83,11 @@ def add_eic(enc, dec):
 def add_filter(enc, dec, entropy: str = DEFAULT_EIC):
     """no_filter.py:14-21 (entropy codec choice lives in the filter module; the
     module -c names is imported there, and CBAHC.py adds --order on import)."""
+    names = "TIFF, z_lib, CBAAC, CBAHC, TCBAAC, TCBAACP, TCBAAC2D"
     enc.add_argument("-c", "--entropy_image_codec",
-                     help=f"Entropy Image Codec (default: {DEFAULT_EIC})", default=DEFAULT_EIC)
+                     help=f"Entropy Image Codec: {names} (default: {DEFAULT_EIC})", default=DEFAULT_EIC)
     dec.add_argument("-c", "--entropy_image_codec",
-                     help=f"Entropy Image Codec (default: {DEFAULT_EIC})", default=DEFAULT_EIC)
+                     help=f"Entropy Image Codec: {names} (default: {DEFAULT_EIC})", default=DEFAULT_EIC)
     if entropy == "CBAHC":
         add_order_cbahc(enc, dec)
 

@@ -295,12 +295,230 @@ inline int renorm(uint32_t &low, uint32_t &high, uint32_t &prefix, int &n_prefix
     return n_prefix + e3;
 }
 
+// ---- container version 4: tiles with a two-dimensional context -------------------------
+// A (H, W, C) u8 frame is coded plane by plane in th x tw tiles (cropped at
+// the edges, numbered channel-major, then tile row, then tile column), each
+// tile's symbols in raster order by the A8 coder above, flushed at the tile's
+// end.  The symbol at (y, x) of a tile takes one of 16 AdaptiveModels:
+// ctx = 4 q(|left - 128|) + q(|up - 128|), q(v) = min(v, 3), a neighbour
+// outside the tile counting as magnitude 0.
+constexpr int kCtx2d = 16;
+
+struct Geom2d {
+    int64_t H, W, C, th, tw, ty, tx, nt;   // ty x tx tiles per plane, nt = C ty tx
+};
+
+inline bool geom2d(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw, Geom2d &g)
+{
+    if (H < 0 || W < 0 || C < 0 || th < 1 || tw < 1) return false;
+    g = {H, W, C, th, tw, (H + th - 1) / th, (W + tw - 1) / tw, 0};
+    g.nt = C * g.ty * g.tx;
+    return true;
+}
+
+inline uint32_t mag3(uint32_t v)
+{
+    const uint32_t a = v >= 128 ? v - 128 : 128 - v;
+    return a < 3 ? a : 3;
+}
+
+// tile t of the frame: its plane, origin and (cropped) size
+struct Tile2d {
+    int64_t c, y0, x0, h, w, in_plane;
+};
+
+inline Tile2d tile2d(const Geom2d &g, int64_t t)
+{
+    Tile2d r;
+    const int64_t per = g.ty * g.tx;
+    r.c = t / per;
+    r.in_plane = t % per;
+    r.y0 = (r.in_plane / g.tx) * g.th;
+    r.x0 = (r.in_plane % g.tx) * g.tw;
+    r.h = g.H - r.y0 < g.th ? g.H - r.y0 : g.th;
+    r.w = g.W - r.x0 < g.tw ? g.W - r.x0 : g.tw;
+    return r;
+}
+
+// the encoder's per-symbol step of cbaac_encode, for a caller that picks the model
+struct Encoder2d {
+    BitWriter bw;
+    const Divider &dv = Divider::get();
+    uint32_t low = 0, high = 0xFFFFFFFFu;
+    uint64_t pending = 0;
+    void put(Model &m, int s)
+    {
+        const uint32_t lo = m.cum(s), hi = lo + m.freq[s], tot = m.total;
+        const uint64_t range = (uint64_t)(high - low) + 1;
+        high = low + dv.div(range * hi, tot) - 1;
+        low = low + dv.div(range * lo, tot);
+        uint32_t prefix;
+        int np, e3;
+        renorm(low, high, prefix, np, e3);
+        if (np) {
+            const uint32_t b = prefix >> (np - 1);
+            bw.put(b, 1);
+            if (pending) {
+                bw.repeat(!b, pending);
+                pending = 0;
+            }
+            bw.put(prefix, np - 1);
+        }
+        pending += (uint64_t)e3;
+        m.update(s);
+    }
+    void flush()
+    {
+        const uint32_t b = low < kQ1 ? 0u : 1u;
+        bw.put(b, 1);
+        bw.repeat(!b, pending + 1);
+        bw.finish();
+    }
+};
+
+// the decoder's per-symbol step of cbaac_decode
+struct Decoder2d {
+    BitReader br;
+    const Divider &dv = Divider::get();
+    uint32_t low = 0, high = 0xFFFFFFFFu, value = 0;
+    void start() { value = br.get(32); }
+    int get(Model &m)
+    {
+        const uint64_t range = (uint64_t)(high - low) + 1;
+        const uint32_t tot = m.total;
+        const uint64_t num = ((uint64_t)(value - low) + 1) * tot - 1;
+        int s = m.mps;
+        uint32_t lo = m.cum(s);
+        if (!((uint64_t)lo * range <= num && num < (uint64_t)(lo + m.freq[s]) * range))
+            s = m.find((uint32_t)(num / range), lo);
+        const uint32_t hi = lo + m.freq[s];
+        high = low + dv.div(range * hi, tot) - 1;
+        low = low + dv.div(range * lo, tot);
+        uint32_t prefix;
+        int np, e3;
+        renorm(low, high, prefix, np, e3);
+        if (np) value = (np == 32 ? 0u : value << np) | br.get(np);
+        if (e3) value = (value & kHalf) | ((value << e3) & 0x7FFFFFFFu) | br.get(e3);
+        m.update(s);
+        return s;
+    }
+};
+
+int check2d(const Geom2d &g, int32_t nclass, const uint16_t *priors)
+{
+    if (nclass < 1 || nclass > 256) return set_error(VCF_ERR_INVALID, "nclass %d (1 .. 256)", nclass);
+    if (!priors) return set_error(VCF_ERR_INVALID, "null priors");
+    for (int64_t r = 0; r < (int64_t)nclass * kCtx2d; ++r) {
+        uint32_t tot = 0;
+        for (int i = 0; i < kSymbols; ++i) {
+            if (priors[r * kSymbols + i] == 0) return set_error(VCF_ERR_INVALID, "prior frequency 0 (row %lld)", (long long)r);
+            tot += priors[r * kSymbols + i];
+        }
+        if (tot >= kMaxFreq) return set_error(VCF_ERR_INVALID, "prior row %lld: total %u >= %u", (long long)r, tot, kMaxFreq);
+    }
+    return VCF_OK;
+}
+
 }  // namespace
 }  // namespace vcf
 
 using namespace vcf;
 
 extern "C" {
+
+int64_t vcf_cbaac2d_tiles(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw)
+{
+    Geom2d g;
+    return geom2d(H, W, C, th, tw, g) ? g.nt : 0;
+}
+
+int vcf_cbaac2d_prior(const uint8_t *sym, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw, int32_t nclass,
+                      uint16_t *priors)
+{
+    Geom2d g;
+    if (!geom2d(H, W, C, th, tw, g)) return set_error(VCF_ERR_INVALID, "bad frame or tile size");
+    if (nclass < 1 || nclass > 256) return set_error(VCF_ERR_INVALID, "nclass %d (1 .. 256)", nclass);
+    if (!priors || (g.nt > 0 && !sym)) return set_error(VCF_ERR_INVALID, "null buffer");
+    const int64_t rows = (int64_t)nclass * kCtx2d, per = g.ty * g.tx;
+    std::vector<uint64_t> hist(rows * kSymbols, 0);
+    for (int64_t t = 0; t < g.nt; ++t) {
+        const Tile2d tl = tile2d(g, t);
+        uint64_t *hc = hist.data() + ((tl.in_plane * nclass) / per) * kCtx2d * kSymbols;
+        for (int64_t y = 0; y < tl.h; ++y)
+            for (int64_t x = 0; x < tl.w; ++x) {
+                const uint8_t *p = sym + ((tl.y0 + y) * W + tl.x0 + x) * C + tl.c;
+                const uint32_t wn = x ? mag3(p[-C]) : 0, nn = y ? mag3(p[-W * C]) : 0;
+                ++hc[(4 * wn + nn) * kSymbols + *p];
+            }
+    }
+    for (int64_t r = 0; r < rows; ++r) {
+        uint64_t n = 0;
+        for (int i = 0; i < kSymbols; ++i) n += hist[r * kSymbols + i];
+        for (int i = 0; i < kSymbols; ++i)
+            priors[r * kSymbols + i] = (uint16_t)(1 + (n ? hist[r * kSymbols + i] * 8192 / n : 0));
+    }
+    return VCF_OK;
+}
+
+int vcf_cbaac2d_encode(const uint8_t *sym, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw, int32_t nclass,
+                       const uint16_t *priors, uint8_t *out, int64_t out_capacity, int64_t *tile_bytes,
+                       int64_t *out_bytes)
+{
+    Geom2d g;
+    if (!geom2d(H, W, C, th, tw, g)) return set_error(VCF_ERR_INVALID, "bad frame or tile size");
+    if (int s = check2d(g, nclass, priors)) return s;
+    if (!out_bytes || out_capacity < 0 || (g.nt > 0 && (!sym || !out || !tile_bytes)))
+        return set_error(VCF_ERR_INVALID, "null buffer");
+    const int64_t per = g.ty * g.tx;
+    std::vector<Model> models(kCtx2d);
+    int64_t o = 0;
+    for (int64_t t = 0; t < g.nt; ++t) {
+        const Tile2d tl = tile2d(g, t);
+        const uint16_t *rows = priors + ((tl.in_plane * nclass) / per) * kCtx2d * kSymbols;
+        for (int c = 0; c < kCtx2d; ++c) models[c].init(rows + c * kSymbols);
+        Encoder2d e{BitWriter{out + o, out_capacity - o}};
+        for (int64_t y = 0; y < tl.h; ++y)
+            for (int64_t x = 0; x < tl.w; ++x) {
+                const uint8_t *p = sym + ((tl.y0 + y) * W + tl.x0 + x) * C + tl.c;
+                const uint32_t wn = x ? mag3(p[-C]) : 0, nn = y ? mag3(p[-W * C]) : 0;
+                e.put(models[4 * wn + nn], *p);
+                if (e.bw.overflow) return set_error(VCF_ERR_INVALID, "output buffer too small");
+            }
+        e.flush();
+        if (e.bw.overflow) return set_error(VCF_ERR_INVALID, "output buffer too small");
+        tile_bytes[t] = (e.bw.nbits + 7) >> 3;
+        o += tile_bytes[t];
+    }
+    *out_bytes = o;
+    return VCF_OK;
+}
+
+int vcf_cbaac2d_decode(const uint8_t *bytes, const int64_t *tile_offsets, int64_t H, int64_t W, int64_t C, int64_t th,
+                       int64_t tw, int32_t nclass, const uint16_t *priors, uint8_t *sym_out)
+{
+    Geom2d g;
+    if (!geom2d(H, W, C, th, tw, g)) return set_error(VCF_ERR_INVALID, "bad frame or tile size");
+    if (int s = check2d(g, nclass, priors)) return s;
+    if (g.nt > 0 && (!tile_offsets || !sym_out)) return set_error(VCF_ERR_INVALID, "null buffer");
+    const int64_t per = g.ty * g.tx;
+    std::vector<Model> models(kCtx2d);
+    for (int64_t t = 0; t < g.nt; ++t) {
+        const Tile2d tl = tile2d(g, t);
+        const int64_t nb = tile_offsets[t + 1] - tile_offsets[t];
+        if (tile_offsets[t] < 0 || nb < 0 || (nb > 0 && !bytes)) return set_error(VCF_ERR_INVALID, "bad tile offsets");
+        const uint16_t *rows = priors + ((tl.in_plane * nclass) / per) * kCtx2d * kSymbols;
+        for (int c = 0; c < kCtx2d; ++c) models[c].init(rows + c * kSymbols);
+        Decoder2d d{BitReader{bytes + tile_offsets[t], nb}};
+        d.start();
+        for (int64_t y = 0; y < tl.h; ++y)
+            for (int64_t x = 0; x < tl.w; ++x) {
+                uint8_t *p = sym_out + ((tl.y0 + y) * W + tl.x0 + x) * C + tl.c;
+                const uint32_t wn = x ? mag3(p[-C]) : 0, nn = y ? mag3(p[-W * C]) : 0;
+                *p = (uint8_t)d.get(models[4 * wn + nn]);
+            }
+    }
+    return VCF_OK;
+}
 
 int64_t vcf_cbaac_bound(int64_t n_symbols)
 {

@@ -1111,6 +1111,276 @@ int check_args(int64_t n, int32_t order, int64_t seg_len)
     return VCF_OK;
 }
 
+// ---- container version 4: tiles with a two-dimensional context ---------------------
+// A (H, W, C) frame is coded plane by plane in th x tw tiles (cropped at the
+// edges), one wave per tile, the tile's symbols in raster order through the
+// same coder and AdaptiveModel as above.  The symbol at (y, x) of a tile
+// takes model ctx = 4 q(|left - 128|) + q(|up - 128|), q(v) = min(v, 3), a
+// neighbour outside the tile counting as 0 (vcf_cbaac.cpp: vcf_cbaac2d_*,
+// whose bytes every tile here equals).
+//   - The 16 models live in LDS as the order-1 tables do: lane l's four
+//     cumulative counts of a model as two packed u16 pairs.  u16 suffices: a
+//     prior row's total is at most 256 + 8192, and the halving rule
+//     (stale total >= 16384) keeps every count <= 16385.  The current
+//     context's model stays in VGPRs; it is written back and another read
+//     only when the context changes (runs of zeros keep context 0).
+//   - The tile's current and previous rows are staged in LDS, read four
+//     symbols (one dword, wave-uniform) at a time: the left neighbour is the
+//     previous symbol, the upper one comes from the other row.  The decoder
+//     writes each decoded dword there and derives the contexts of the next
+//     row from it.
+//   LDS per wave: 16 x 64 x 8 B models + 16 x 4 B totals + 2 x 256 B rows =
+//   8768 B, so 18 waves fit a CU's 160 KiB (4.5 per SIMD); the kernels need
+//   no more registers than that allows.
+constexpr int kCtx2d = 16;
+constexpr int kMaxTw = 256;             // widest tile (two rows of it in LDS)
+constexpr int64_t kMaxTile = 65536;     // symbols per tile
+
+struct Geom2d {
+    int64_t H, W, C, th, tw, ty, tx;    // ty x tx tiles per plane
+};
+
+struct Lds2d {
+    uint2 c[kCtx2d * 64];               // model k: lane l's (p0, p1) at c[64 k + l]
+    uint32_t total[kCtx2d];
+    alignas(4) uint8_t row[2][kMaxTw];  // row y of the tile in row[y & 1]
+};
+
+// tile t of a frame: its first symbol's offset in the frame, its size, its place in the plane
+struct Tile2d {
+    int64_t base, in_plane;
+    int32_t h, w;
+};
+
+__device__ __forceinline__ Tile2d tile2d(const Geom2d &g, int64_t t)
+{
+    Tile2d r;
+    const int64_t per = g.ty * g.tx, c = t / per;
+    r.in_plane = t - c * per;
+    const int64_t y0 = (r.in_plane / g.tx) * g.th, x0 = (r.in_plane % g.tx) * g.tw;
+    r.h = (int32_t)(g.H - y0 < g.th ? g.H - y0 : g.th);
+    r.w = (int32_t)(g.W - x0 < g.tw ? g.W - x0 : g.tw);
+    r.base = (y0 * g.W + x0) * g.C + c;
+    return r;
+}
+
+__device__ __forceinline__ uint32_t mag3(uint32_t v)
+{
+    const uint32_t a = v >= 128 ? v - 128 : 128 - v;
+    return a < 3 ? a : 3;
+}
+
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+__device__ __forceinline__ void lds2d_read(const Lds2d &L, uint32_t k, uint32_t lane, Model &m)
+{
+    const uint2 v = L.c[k * 64 + lane];
+    m.p0 = v.x;
+    m.p1 = v.y;
+    m.total = uniform(L.total[k]);
+}
+
+__device__ __forceinline__ void lds2d_write(Lds2d &L, uint32_t k, uint32_t lane, const Model &m)
+{
+    L.c[k * 64 + lane] = make_uint2(m.p0, m.p1);
+    if (lane == 0) L.total[k] = m.total;
+}
+
+// the tile's 16 models from its class's 16 prior rows; model 0 is left in m
+__device__ __forceinline__ void lds2d_init(Lds2d &L, const uint16_t *__restrict__ rows, uint32_t lane, Model &m)
+{
+    for (int k = kCtx2d - 1; k >= 0; --k) {
+        model_reset_prior(m, rows + 256 * k, lane);
+        lds2d_write(L, (uint32_t)k, lane, m);
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void cbaac2d_encode_kernel(const uint8_t *__restrict__ sym, Geom2d g,
+                                                            uint32_t *__restrict__ slots, int64_t slot_words,
+                                                            int64_t *__restrict__ tile_bits,
+                                                            const uint16_t *__restrict__ priors, Frames fr)
+{
+    __shared__ Lds2d L;
+    const int64_t f = blockIdx.y, t = blockIdx.x, per = g.ty * g.tx, nt = g.C * per;
+    const uint32_t lane = threadIdx.x;
+    const Tile2d tl = tile2d(g, t);
+    const uint8_t *src = sym + f * fr.sym_stride + tl.base;
+    const int64_t rs = g.W * g.C;
+    Model m;
+    lds2d_init(L, priors + f * fr.prior_stride + ((tl.in_plane * fr.nclass) / per) * (kCtx2d * 256), lane, m);
+    uint32_t ctx = 0;
+
+    BitWriter w;
+    w.out = slots + (f * nt + t) * slot_words;
+    Encoder e;
+    for (int32_t y = 0; y < tl.h; ++y) {
+        uint8_t *cur = L.row[y & 1];
+        const uint8_t *up = L.row[(y & 1) ^ 1];
+        __syncthreads();   // row y - 2 has been read
+        for (int32_t x = (int32_t)lane; x < tl.w; x += 64) cur[x] = src[y * rs + (int64_t)x * g.C];
+        __syncthreads();
+        uint32_t wn = 0;
+        for (int32_t x4 = 0; x4 < tl.w; x4 += 4) {
+            const uint32_t cw = uniform(*reinterpret_cast<const uint32_t *>(cur + x4));
+            const uint32_t uw = y ? uniform(*reinterpret_cast<const uint32_t *>(up + x4)) : 0x80808080u;
+            const int cnt = tl.w - x4 < 4 ? tl.w - x4 : 4;
+            for (int j = 0; j < cnt; ++j) {
+                const uint32_t s = (cw >> (8 * j)) & 255u;
+                const uint32_t k = 4 * wn + mag3((uw >> (8 * j)) & 255u);
+                if (k != ctx) {
+                    lds2d_write(L, ctx, lane, m);
+                    lds2d_read(L, k, lane, m);
+                    ctx = k;
+                }
+                const uint32_t tot = m.total;
+                uint32_t lo, hi;
+                model_range(m, s, lo, hi);
+                e.code(lo, hi, (double)tot, rcp_exact(tot), w, lane);
+                model_update(m, s, lane);
+                wn = mag3(s);
+            }
+        }
+    }
+    e.flush(w, lane);
+    const uint64_t bits = w.finish(lane);
+    if (lane == 0) tile_bits[f * nt + t] = (int64_t)bits;
+}
+
+// one symbol of the A8 decoder with model m (the body of cbaac_tiled_decode_kernel's loop)
+__device__ __forceinline__ uint32_t decode_step(Model &m, BitReader &br, uint32_t &low, uint32_t &high,
+                                                uint32_t &value, uint32_t lane)
+{
+    const double tot = (double)m.total;
+    const double inv = rcp_nr(tot);
+    const uint32_t span = high - low;
+    const double rng = (double)span + 1.0;
+    const uint32_t T = value - low;
+    const uint32_t f0 = (uint32_t)floordiv(rng * (double)(m.p0 & 0xFFFFu), tot, inv);
+    const uint32_t f1 = (uint32_t)floordiv(rng * (double)(m.p0 >> 16), tot, inv);
+    const uint32_t f2 = (uint32_t)floordiv(rng * (double)(m.p1 & 0xFFFFu), tot, inv);
+    const uint32_t f3 = (uint32_t)floordiv(rng * (double)(m.p1 >> 16), tot, inv);
+    const uint32_t Ln = (uint32_t)__popcll(__ballot(f0 <= T)) - 1;
+    const uint32_t g0 = rl(f0, Ln), g1 = rl(f1, Ln), g2 = rl(f2, Ln), g3 = rl(f3, Ln);
+    const uint32_t g4m1 = Ln == 63 ? span : rl(f0, (Ln + 1) & 63) - 1;
+    const uint32_t j = (T >= g1 ? 1u : 0u) + (T >= g2 ? 1u : 0u) + (T >= g3 ? 1u : 0u);
+    const uint32_t s = 4 * Ln + j;
+    const uint32_t ql = j == 0 ? g0 : j == 1 ? g1 : j == 2 ? g2 : g3;
+    const uint32_t qhm1 = j == 0 ? g1 - 1 : j == 1 ? g2 - 1 : j == 2 ? g3 - 1 : g4m1;
+    high = low + qhm1;
+    low = low + ql;
+    const uint32_t d = __builtin_clz(low ^ high);
+    if (d) {
+        low <<= d;
+        high = (high << d) | ((1u << d) - 1u);
+        value = (value << d) | br.get(d, lane);
+    }
+    const uint32_t x = (low << 1) & ~(high << 1);
+    const uint32_t p = __builtin_clz(~x);
+    if (p) {
+        low = (low << p) & 0x7FFFFFFFu;
+        high = (high << p) | ((1u << p) - 1u) | 0x80000000u;
+        value = ((value << p) ^ 0x80000000u) | br.get(p, lane);
+    }
+    model_update(m, s, lane);
+    return s;
+}
+
+__global__ __launch_bounds__(64) void cbaac2d_decode_kernel(const uint8_t *__restrict__ in,
+                                                            const int64_t *__restrict__ offs, Geom2d g,
+                                                            uint8_t *__restrict__ out,
+                                                            const uint16_t *__restrict__ priors, Frames fr)
+{
+    __shared__ Lds2d L;
+    const int64_t f = blockIdx.y, t = blockIdx.x, per = g.ty * g.tx, nt = g.C * per;
+    const uint32_t lane = threadIdx.x;
+    const Tile2d tl = tile2d(g, t);
+    uint8_t *dst = out + f * fr.out_stride + tl.base;
+    const int64_t rs = g.W * g.C;
+    offs += f * (nt + 1);
+    Model m;
+    lds2d_init(L, priors + f * fr.prior_stride + ((tl.in_plane * fr.nclass) / per) * (kCtx2d * 256), lane, m);
+    uint32_t ctx = 0;
+
+    BitReader br;
+    br.src = in + offs[t];
+    br.nbytes = offs[t + 1] - offs[t];
+    br.start(lane);
+    uint32_t low = 0, high = 0xFFFFFFFFu, value = br.get(32, lane);
+    for (int32_t y = 0; y < tl.h; ++y) {
+        uint8_t *cur = L.row[y & 1];
+        const uint8_t *up = L.row[(y & 1) ^ 1];
+        __syncthreads();   // row y - 1 is whole, row y - 2 has gone out
+        uint32_t wn = 0;
+        for (int32_t x4 = 0; x4 < tl.w; x4 += 4) {
+            const uint32_t uw = y ? uniform(*reinterpret_cast<const uint32_t *>(up + x4)) : 0x80808080u;
+            const int cnt = tl.w - x4 < 4 ? tl.w - x4 : 4;
+            uint32_t acc = 0;
+            for (int j = 0; j < cnt; ++j) {
+                const uint32_t k = 4 * wn + mag3((uw >> (8 * j)) & 255u);
+                if (k != ctx) {
+                    lds2d_write(L, ctx, lane, m);
+                    lds2d_read(L, k, lane, m);
+                    ctx = k;
+                }
+                const uint32_t s = decode_step(m, br, low, high, value, lane);
+                acc |= s << (8 * j);
+                wn = mag3(s);
+            }
+            if (lane == 0) *reinterpret_cast<uint32_t *>(cur + x4) = acc;
+        }
+        __syncthreads();
+        for (int32_t x = (int32_t)lane; x < tl.w; x += 64) dst[y * rs + (int64_t)x * g.C] = cur[x];
+    }
+}
+
+// per-(class, context) histograms: one workgroup per tile (its class is
+// fixed), LDS bins, one global atomic per used bin and tile
+__global__ __launch_bounds__(256) void cbaac2d_hist_kernel(const uint8_t *__restrict__ sym, Geom2d g, int32_t nclass,
+                                                           uint32_t *__restrict__ hist, int64_t sym_stride)
+{
+    __shared__ uint32_t bins[kCtx2d * 256];
+    const int64_t f = blockIdx.y, per = g.ty * g.tx;
+    const Tile2d tl = tile2d(g, blockIdx.x);
+    const uint8_t *src = sym + f * sym_stride + tl.base;
+    const int64_t rs = g.W * g.C;
+    hist += (kCtx2d * 256) * (f * nclass + (tl.in_plane * nclass) / per);
+    for (int i = threadIdx.x; i < kCtx2d * 256; i += 256) bins[i] = 0;
+    __syncthreads();
+    const int32_t n = tl.h * tl.w;
+    for (int32_t i = threadIdx.x; i < n; i += 256) {
+        const int32_t y = i / tl.w, x = i - y * tl.w;
+        const uint8_t *p = src + y * rs + (int64_t)x * g.C;
+        const uint32_t wn = x ? mag3(p[-g.C]) : 0u, nn = y ? mag3(p[-rs]) : 0u;
+        atomicAdd(&bins[(4 * wn + nn) * 256 + *p], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kCtx2d * 256; i += 256)
+        if (bins[i]) atomicAdd(&hist[i], bins[i]);
+}
+
+// words per tile slot, even: the int64 tables behind the slots stay 8-byte aligned
+int64_t slot_words_2d(int64_t tile_symbols) { return (slot_words_for(tile_symbols) + 1) & ~(int64_t)1; }
+
+int check_2d(int64_t n_frames, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw, int32_t nclass,
+             const void *priors_dev, Geom2d &g)
+{
+    if (H < 0 || W < 0 || C < 0) return set_error(VCF_ERR_INVALID, "negative frame size");
+    if (H > 0 && W > 0 && C > 0 && (W > INT64_MAX / H || C > INT64_MAX / (H * W)))
+        return set_error(VCF_ERR_INVALID, "frame size overflows");
+    if (th < 1 || tw < 1) return set_error(VCF_ERR_INVALID, "tile size %lld x %lld", (long long)th, (long long)tw);
+    if (tw > kMaxTw || th * tw > kMaxTile || th > kMaxTile)
+        return set_error(VCF_ERR_UNSUPPORTED, "tiled CBAAC 2-D on the GPU: tiles up to %d wide and %lld symbols", kMaxTw,
+                         (long long)kMaxTile);
+    if (n_frames < 1 || n_frames > 65535) return set_error(VCF_ERR_INVALID, "n_frames %lld (1 .. 65535)", (long long)n_frames);
+    if (nclass < 1 || nclass > kMaxClasses) return set_error(VCF_ERR_INVALID, "nclass %d (1 .. %d)", nclass, kMaxClasses);
+    if (priors_dev && (reinterpret_cast<uintptr_t>(priors_dev) & 7))
+        return set_error(VCF_ERR_INVALID, "priors_dev not 8-byte aligned");
+    g = {H, W, C, th, tw, (H + th - 1) / th, (W + tw - 1) / tw};
+    if (C * g.ty * g.tx > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many tiles");
+    return VCF_OK;
+}
+
 }  // namespace
 }  // namespace vcf
 
@@ -1376,6 +1646,95 @@ int vcf_cbaac_tiled_decode_classes(const uint8_t *in_dev, const int64_t *seg_off
     if (frame_symbols > 0 && !priors_dev) return set_error(VCF_ERR_INVALID, "null prior");
     return tiled_decode(in_dev, seg_offsets_dev, n_frames, frame_symbols, order, seg_len, sym_dev, out_frame_stride,
                         stream, priors_dev, 256LL * nclass, nclass);
+}
+
+// ---- version 4: tiles with a two-dimensional context ----------------------------------
+int64_t vcf_cbaac_tiled2d_tiles(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw)
+{
+    if (H <= 0 || W <= 0 || C <= 0 || th < 1 || tw < 1) return 0;
+    return C * ((H + th - 1) / th) * ((W + tw - 1) / tw);
+}
+
+int64_t vcf_cbaac_tiled2d_workspace(int64_t n_frames, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw)
+{
+    const int64_t nt = vcf_cbaac_tiled2d_tiles(H, W, C, th, tw);
+    if (nt == 0 || n_frames <= 0) return 0;
+    // slots, per-tile bit counts, byte offsets (nt + 1), per frame
+    return n_frames * (nt * slot_words_2d(th * tw) * 4 + nt * 8 + (nt + 1) * 8);
+}
+
+int64_t vcf_cbaac_tiled2d_bound(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw)
+{
+    const int64_t nt = vcf_cbaac_tiled2d_tiles(H, W, C, th, tw);
+    return nt == 0 ? 0 : nt * slot_words_2d(th * tw) * 4;
+}
+
+int vcf_cbaac_tiled2d_prior_frames(const uint8_t *sym_dev, int64_t n_frames, int64_t H, int64_t W, int64_t C,
+                                   int64_t frame_stride, int64_t th, int64_t tw, int32_t nclass, uint16_t *priors_dev,
+                                   uint32_t *hist_dev, void *stream)
+{
+    Geom2d g;
+    if (int s = check_2d(n_frames, H, W, C, th, tw, nclass, priors_dev, g)) return s;
+    const int64_t nt = C * g.ty * g.tx;
+    if (!priors_dev || !hist_dev || (nt > 0 && !sym_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t rows = n_frames * nclass * kCtx2d;
+    if (int s = hip_check(hipMemsetAsync(hist_dev, 0, 256 * sizeof(uint32_t) * rows, st), "hipMemsetAsync")) return s;
+    if (nt > 0) {
+        cbaac2d_hist_kernel<<<dim3((unsigned)nt, (unsigned)n_frames), 256, 0, st>>>(sym_dev, g, nclass, hist_dev,
+                                                                                   frame_stride);
+        if (int s = hip_check(hipGetLastError(), "cbaac2d_hist_kernel")) return s;
+    }
+    cbaac_prior_classes_kernel<<<(unsigned)rows, 256, 0, st>>>(hist_dev, priors_dev);
+    return hip_check(hipGetLastError(), "cbaac_prior_classes_kernel");
+}
+
+int vcf_cbaac_tiled2d_encode_frames(const uint8_t *sym_dev, int64_t n_frames, int64_t H, int64_t W, int64_t C,
+                                    int64_t frame_stride, const uint16_t *priors_dev, int32_t nclass, int64_t th,
+                                    int64_t tw, uint8_t *out_dev, int64_t out_frame_capacity, int64_t *tile_bytes_dev,
+                                    void *ws_dev, void *stream)
+{
+    Geom2d g;
+    if (int s = check_2d(n_frames, H, W, C, th, tw, nclass, priors_dev, g)) return s;
+    if (out_frame_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
+    if (!tile_bytes_dev) return set_error(VCF_ERR_INVALID, "null tile_bytes");
+    const int64_t nt = C * g.ty * g.tx;
+    hipStream_t st = (hipStream_t)stream;
+    if (nt == 0) return hip_check(hipMemsetAsync(tile_bytes_dev, 0, 8 * n_frames, st), "hipMemsetAsync");
+    if (!sym_dev || !ws_dev || !out_dev || !priors_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    const int64_t sw = slot_words_2d(th * tw);
+    uint32_t *slots = (uint32_t *)ws_dev;
+    int64_t *bits = (int64_t *)(slots + n_frames * nt * sw);
+    int64_t *offs = bits + n_frames * nt;
+    Frames fr;
+    fr.sym_stride = frame_stride;
+    fr.prior_stride = 256LL * kCtx2d * nclass;
+    fr.nclass = nclass;
+    const dim3 grid((unsigned)nt, (unsigned)n_frames);
+    cbaac2d_encode_kernel<<<grid, 64, 0, st>>>(sym_dev, g, slots, sw, bits, priors_dev, fr);
+    if (int s = hip_check(hipGetLastError(), "cbaac2d_encode_kernel")) return s;
+    cbaac_tiled_scan_kernel<<<(unsigned)n_frames, 1024, 0, st>>>(bits, nt, offs, tile_bytes_dev);
+    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_scan_kernel")) return s;
+    cbaac_tiled_pack_kernel<<<grid, 256, 0, st>>>(slots, sw, offs, out_dev, out_frame_capacity);
+    return hip_check(hipGetLastError(), "cbaac_tiled_pack_kernel");
+}
+
+int vcf_cbaac_tiled2d_decode_frames(const uint8_t *in_dev, const int64_t *tile_offsets_dev, int64_t n_frames, int64_t H,
+                                    int64_t W, int64_t C, const uint16_t *priors_dev, int32_t nclass, int64_t th,
+                                    int64_t tw, uint8_t *sym_dev, int64_t out_frame_stride, void *stream)
+{
+    Geom2d g;
+    if (int s = check_2d(n_frames, H, W, C, th, tw, nclass, priors_dev, g)) return s;
+    const int64_t nt = C * g.ty * g.tx;
+    if (nt == 0) return VCF_OK;
+    if (!in_dev || !tile_offsets_dev || !sym_dev || !priors_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    Frames fr;
+    fr.out_stride = out_frame_stride;
+    fr.prior_stride = 256LL * kCtx2d * nclass;
+    fr.nclass = nclass;
+    cbaac2d_decode_kernel<<<dim3((unsigned)nt, (unsigned)n_frames), 64, 0, (hipStream_t)stream>>>(
+        in_dev, tile_offsets_dev, g, sym_dev, priors_dev, fr);
+    return hip_check(hipGetLastError(), "cbaac2d_decode_kernel");
 }
 
 }  // extern "C"

@@ -32,8 +32,24 @@ indices is ~20 bytes: a uint32 index would cost +4.8 % of the stream).
 With the DCT's subband layout and nclass = 8 a row is about one subband row,
 whose statistics differ the most: 4096-symbol segments (1519 waves for a 1080p
 frame) then cost about the serial stream's rate.
-decompress() of a malformed header returns zeros((10, 10)) like
-CBAAC.py:101-102.
+Version 4 (`-c TCBAAC2D`, `ctx2d=True`; not in the reference, whose TODO.md
+asks for it: "Adapt CBAAC to images, shapping the context") codes a (H, W, C)
+or (H, W) array plane by plane in th x tw tiles (64 x 64 by default, cropped
+at the edges, numbered channel-major, then tile row, then tile column), a
+tile's symbols in raster order through the same coder and AdaptiveModel,
+flushed at the tile's end, one wave per tile.  The symbol at (y, x) of a tile
+takes one of 16 models: ctx = 4 q(|left - 128|) + q(|up - 128|), q(v) =
+min(v, 3), a neighbour outside the tile counting as 0 -- in the DCT's subband
+layout the neighbours are the same coefficient of the adjacent blocks.  Tile
+t of a plane's n_t takes prior class floor(t nclass / n_t); its 16 models
+start from the class's 16 rows, row (class, ctx) = 1 + floor(hist[s] * 8192 /
+n) over the class's symbols in that context (all ones where there are none).
+    uint32 ndims, uint32 shape[ndims], b"VCFT", uint32 version = 4,
+    uint32 th, uint32 tw, uint32 n_tiles, uint32 nclass, uint32 nctx = 16,
+    the nclass * nctx prior rows (version 3's sparse rows),
+    the tile sizes (LEB128 varints), the tiles' bit streams back to back
+decompress() reads all four versions; a malformed header returns
+zeros((10, 10)) like CBAAC.py:101-102.
 """
 from __future__ import annotations
 
@@ -55,6 +71,9 @@ DEFAULT_SEG = 1 << 17     # 48 segments for a 1080p frame, 190 for 4K
 PRIOR_SEG = 1 << 15       # version 2: 190 segments for 1080p at +2.3 % rate (profiles/r02_tcbaac_prior.jsonl)
 CLASS_SEG = 1 << 12       # version 3 (-c TCBAACP): 1519 segments for 1080p
 PRIOR_CLASSES = 8         # version 3's prior rows per frame (the 8 subband rows of the 8x8 DCT)
+VERSION_2D = 4
+TILE_2D = (64, 64)        # version 4's tile (th, tw): CLASS_SEG symbols
+NCTX_2D = 16              # version 4's contexts per class
 
 
 def n_segments(n: int, seg_len: int = DEFAULT_SEG) -> int:
@@ -308,12 +327,14 @@ class FrameBatch:
             if self.n_frames:
                 self.sizes_dev.download(allz, self.stream)
                 if self.prior:
-                    shp = (self.n_frames, self.nclass, 256) if self.nclass > 1 else (self.n_frames, 256)
-                    self._priors = np.empty(shp, np.uint16)
+                    self._priors = np.empty(self._prior_shape(), np.uint16)
                     self.prior_dev.download(self._priors, self.stream)
             self.stream.synchronize()
             self._sizes = allz
         return self._sizes[:, :-1], self._sizes[:, -1].copy(), self._priors
+
+    def _prior_shape(self):
+        return (self.n_frames, self.nclass, 256) if self.nclass > 1 else (self.n_frames, 256)
 
     def payload(self, f: int):
         """(device buffer, byte offset, byte count) of frame f's packed segments."""
@@ -368,6 +389,221 @@ def encode_frames_device(sym: DeviceBuffer, n_frames: int, frame_symbols: int, o
     fb = FrameBatch(n_frames, frame_symbols, order, seg_len, prior, nclass=nclass)
     fb.launch(sym, offset, after)
     return fb.download()
+
+
+def frame_dims(shape):
+    """Version 4's (H, W, C) of an array shape: (H, W, C), or (H, W) with C = 1."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) == 2:
+        return shape + (1,)
+    if len(shape) == 3:
+        return shape
+    raise ValueError(f"2-D context: a (H, W, C) or (H, W) array, not {len(shape)} dimensions")
+
+
+def n_tiles2d(shape, th: int, tw: int) -> int:
+    H, W, C = frame_dims(shape)
+    return int(L.lib().vcf_cbaac2d_tiles(H, W, C, int(th), int(tw)))
+
+
+def check_rows2d(priors, nclass: int) -> np.ndarray:
+    """Version 4's nclass x 16 prior rows as a (nclass * 16, 256) uint16 array:
+    every frequency >= 1, every row's total below the model's max_freq."""
+    priors = np.ascontiguousarray(priors, np.uint16)
+    if (not 1 <= int(nclass) <= 256 or priors.size != int(nclass) * NCTX_2D * 256 or int(priors.min()) < 1
+            or int(priors.reshape(-1, 256).sum(axis=1, dtype=np.int64).max()) >= 16384):
+        raise ValueError("bad prior table")
+    return priors.reshape(-1, 256)
+
+
+class FrameBatch2D(FrameBatch):
+    """FrameBatch for container version 4: `n_frames` frames of one shape,
+    each coded in tiles with the two-dimensional context, one launch per
+    stage (vcf_cbaac_tiled2d_*_frames).  `ns` counts tiles, sizes() returns
+    the tile byte counts and the (n_frames, nclass * 16, 256) prior rows."""
+
+    def __init__(self, n_frames: int, shape, tile=TILE_2D, nclass: int = PRIOR_CLASSES, stream: Stream | None = None):
+        lib = L.lib()
+        self.n_frames = int(n_frames)
+        self.shape = tuple(int(s) for s in shape)
+        self.H, self.W, self.C = frame_dims(self.shape)
+        self.n = self.H * self.W * self.C
+        self.th, self.tw = int(tile[0]), int(tile[1])
+        self.order, self.seg_len, self.prior, self.nclass = 0, self.th * self.tw, True, int(nclass)
+        if self.th < 1 or self.tw < 1 or not 1 <= self.nclass <= 256:
+            raise ValueError("tile sizes >= 1, 1 .. 256 prior classes")
+        dims = (self.H, self.W, self.C, self.th, self.tw)
+        self.ns = int(lib.vcf_cbaac_tiled2d_tiles(*dims))
+        self.cap = int(lib.vcf_cbaac_tiled2d_bound(*dims))
+        self.stream = stream if stream is not None else Stream()
+        nf = max(self.n_frames, 1)
+        self.ws = DeviceBuffer(max(int(lib.vcf_cbaac_tiled2d_workspace(nf, *dims)), 1))
+        self.out = DeviceBuffer(max(self.cap * nf, 1))
+        self.sizes_dev = DeviceBuffer(8 * (self.ns + 1) * nf)
+        self.prior_dev = DeviceBuffer(512 * NCTX_2D * nf * self.nclass)
+        self.hist = DeviceBuffer(1024 * NCTX_2D * nf * self.nclass)
+        self._sizes = None
+        self._priors = None
+
+    def launch(self, sym: DeviceBuffer, offset: int = 0, after: Stream | None = None,
+               frame_stride: int | None = None) -> None:
+        from .device import Event
+        if after is not None and after is not self.stream:
+            ev = Event()
+            ev.record(after)
+            self.stream.wait_event(ev)
+        self._sizes = None
+        if not self.n_frames:
+            return
+        stride = self.n if frame_stride is None else int(frame_stride)
+        base, h = sym.address(offset), self.stream.handle
+        L.call("vcf_cbaac_tiled2d_prior_frames", base, self.n_frames, self.H, self.W, self.C, stride, self.th, self.tw,
+               self.nclass, self.prior_dev.ptr, self.hist.ptr, h)
+        L.call("vcf_cbaac_tiled2d_encode_frames", base, self.n_frames, self.H, self.W, self.C, stride,
+               self.prior_dev.ptr, self.nclass, self.th, self.tw, self.out.ptr, self.cap, self.sizes_dev.ptr,
+               self.ws.ptr, h)
+
+    def _prior_shape(self):
+        return (self.n_frames, self.nclass * NCTX_2D, 256)
+
+    def header(self, f: int, shape=None) -> bytes:
+        tiles, _, pri = self.sizes()
+        return pack2d(self.shape if shape is None else tuple(shape), self.th, self.tw, self.nclass, pri[f], tiles[f], b"")
+
+    def headers(self, shape=None) -> list:
+        """Every frame's header (== header(f)), the sparse rows and varints of all frames at once."""
+        tiles, _, pri = self.sizes()
+        if not self.n_frames:
+            return []
+        shape = self.shape if shape is None else tuple(shape)
+        for f in range(self.n_frames):
+            check_rows2d(pri[f], self.nclass)
+        fixed = _head2d(shape, self.th, self.tw, self.ns, self.nclass)
+        rb, rend = _sparse_rows_batch(pri)
+        vb, vend = _varints_rows(tiles)
+        rst = np.concatenate([[0], rend[:-1]])
+        vst = np.concatenate([[0], vend[:-1]])
+        return [fixed + rb[rst[f] + 4:rend[f]] + vb[vst[f]:vend[f]] for f in range(self.n_frames)]
+
+
+class Tiled2DCoder:
+    """The version-4 GPU calls for one frame at a time, with a stream, a lock
+    (as TiledCoder: the block codecs call the entropy codec from a thread
+    pool) and the device state of the last shape kept for the next call."""
+
+    def __init__(self, tile=TILE_2D, nclass: int = PRIOR_CLASSES, stream: Stream | None = None):
+        self.tile, self.nclass = (int(tile[0]), int(tile[1])), int(nclass)
+        self.stream = stream if stream is not None else Stream()
+        self.scratch = _Scratch()
+        self.last_prior = None
+        self.lock = threading.RLock()
+        self._fb = None
+
+    def _batch(self, shape) -> FrameBatch2D:
+        shape = tuple(int(s) for s in shape)
+        if self._fb is None or self._fb.shape != shape:
+            self._fb = FrameBatch2D(1, shape, self.tile, self.nclass, self.stream)
+        return self._fb
+
+    def encode_device(self, sym: DeviceBuffer, shape, offset: int = 0):
+        """A frame already in HBM -> (tile byte counts, payload bytes); its
+        prior rows are left in self.last_prior."""
+        with self.lock:
+            fb = self._batch(shape)
+            fb.launch(sym, offset)
+            tiles, payload, pri = fb.download()[0]
+            self.last_prior = pri
+            return tiles, payload
+
+    def encode(self, img: np.ndarray):
+        img = np.ascontiguousarray(img, np.uint8)
+        with self.lock:
+            buf = self.scratch.get("sym", img.size)
+            if img.size:
+                buf.upload(img, self.stream)
+            return self.encode_device(buf, img.shape)
+
+    def decode(self, payload: bytes, tile_bytes, shape, priors, nclass: int | None = None) -> np.ndarray:
+        nclass = self.nclass if nclass is None else int(nclass)
+        H, W, C = frame_dims(shape)
+        th, tw = self.tile
+        priors = check_rows2d(priors, nclass)
+        tile_bytes = np.asarray(tile_bytes, np.int64)
+        offs = np.zeros(tile_bytes.size + 1, np.int64)
+        np.cumsum(tile_bytes, out=offs[1:])
+        if tile_bytes.size != n_tiles2d(shape, th, tw) or int(offs[-1]) != len(payload):
+            raise ValueError("tile sizes do not match the frame or the payload")
+        n = H * W * C
+        res = np.empty(tuple(int(s) for s in shape), np.uint8)
+        with self.lock:
+            src = self.scratch.get("in", len(payload))
+            if len(payload):
+                src.upload(np.frombuffer(payload, np.uint8), self.stream)
+            ob = self.scratch.get("offs", offs.nbytes)
+            ob.upload(offs, self.stream)
+            pr = self.scratch.get("prior_in", priors.nbytes)
+            pr.upload(priors, self.stream)
+            out = self.scratch.get("dec", n)
+            L.call("vcf_cbaac_tiled2d_decode_frames", src.ptr, ob.ptr, 1, H, W, C, pr.ptr, nclass, th, tw, out.ptr, n,
+                   self.stream.handle)
+            if n:
+                out.download(res, self.stream)
+            self.stream.synchronize()
+        return res
+
+
+def _head2d(shape, th: int, tw: int, n_tiles: int, nclass: int) -> bytes:
+    return (np.array([len(shape), *shape], np.uint32).tobytes() + MAGIC +
+            struct.pack("<IIIIII", VERSION_2D, th, tw, n_tiles, nclass, NCTX_2D))
+
+
+def pack2d(shape, th: int, tw: int, nclass: int, priors, tile_bytes, payload: bytes) -> bytes:
+    """The version-4 container."""
+    tile_bytes = np.asarray(tile_bytes, np.int64)
+    rows = check_rows2d(priors, nclass)
+    return (_head2d(tuple(shape), th, tw, tile_bytes.size, nclass) + _sparse_rows(rows)[4:] + _varints(tile_bytes) +
+            payload)
+
+
+def container_version(data: bytes) -> int:
+    """The version field of a `.tadpt_arith` container; ValueError if it is not one."""
+    nd = struct.unpack_from("<I", data, 0)[0]
+    if nd > 16:
+        raise ValueError("ndims")
+    p = 4 + 4 * nd
+    if data[p:p + 4] != MAGIC:
+        raise ValueError("not a tiled CBAAC stream")
+    return struct.unpack_from("<I", data, p + 4)[0]
+
+
+def _parse2d(data: bytes):
+    """A version-4 container -> (shape, th, tw, nclass, prior rows, tile byte
+    counts, payload); ValueError / struct.error if malformed (all checks on
+    the host, before any device work)."""
+    if container_version(data) != VERSION_2D:
+        raise ValueError("not a version-4 stream")
+    nd = struct.unpack_from("<I", data, 0)[0]
+    shape = tuple(int(s) for s in struct.unpack_from(f"<{nd}I", data, 4))
+    p = 4 + 4 * nd + 4
+    _, th, tw, nt, nclass, nctx = struct.unpack_from("<IIIIII", data, p)
+    p += 24
+    if nd not in (2, 3):
+        raise ValueError(f"{nd} dimensions")
+    if th < 1 or tw < 1:
+        raise ValueError(f"tile {th} x {tw}")
+    if nctx != NCTX_2D:
+        raise ValueError(f"{nctx} contexts")
+    if not 1 <= nclass <= 256:
+        raise ValueError(f"{nclass} prior classes")
+    if nt != n_tiles2d(shape, th, tw):
+        raise ValueError("tile count does not match the shape")
+    rows, p = _parse_rows(data, p, nclass * NCTX_2D)
+    rows = check_rows2d(rows, nclass)
+    tile_bytes, p = _parse_varints(data, p, nt)
+    payload = data[p:]
+    if int(tile_bytes.sum()) != len(payload):
+        raise ValueError("tile index does not match the payload")
+    return shape, int(th), int(tw), int(nclass), rows, tile_bytes, payload
 
 
 def _varints_rows(v: np.ndarray):
@@ -425,16 +661,21 @@ def _parse_sparse_rows(data: bytes, p: int):
     (K,) = struct.unpack_from("<I", data, p)
     if not 1 <= K <= 256:
         raise ValueError(f"{K} prior classes")
-    p += 4
-    prior = np.ones((K, 256), np.uint16)
-    for c in range(K):
+    prior, p = _parse_rows(data, p + 4, K)
+    return check_prior(prior), p
+
+
+def _parse_rows(data: bytes, p: int, rows: int):
+    """`rows` sparse prior rows at data[p:] -> ((rows, 256) uint16, the offset after them)."""
+    prior = np.ones((rows, 256), np.uint16)
+    for c in range(rows):
         (m,) = struct.unpack_from("<H", data, p)
         if m > 256 or p + 2 + 3 * m > len(data):
             raise ValueError("prior row")
         sy = np.frombuffer(data, np.uint8, m, p + 2)
         prior[c, sy] = np.frombuffer(data, "<u2", m, p + 2 + m)
         p += 2 + 3 * m
-    return check_prior(prior), p
+    return prior, p
 
 
 def pack(shape, order: int, seg_len: int, seg_bytes, payload: bytes, prior=None) -> bytes:
@@ -491,33 +732,115 @@ def _parse(data: bytes):
     return tuple(int(s) for s in shape), int(order), int(seg_len), seg_bytes, payload, prior
 
 
-class TiledCBAACCodec:
-    """The entropy-codec surface of CBAAC.CoDec (compress/decompress,
-    file_extension; CBAAC.py:72-156) over the tiled GPU coder."""
+class _Container:
+    """What the GPU codec and the host codec share: the parameters and the
+    reader of the `.tadpt_arith` container, all four versions."""
 
     file_extension = FILE_EXTENSION
 
-    def __init__(self, order: int = 0, seg_len: int = DEFAULT_SEG, prior: bool = False, nclass: int = 1):
+    def __init__(self, order: int = 0, seg_len: int = DEFAULT_SEG, prior: bool = False, nclass: int = 1,
+                 ctx2d: bool = False, tile=TILE_2D):
+        """ctx2d: write container version 4 (tiles of `tile` = (th, tw) with
+        the two-dimensional context and `nclass` prior classes; order 0)."""
         self.ORDER = int(order)
         self.seg_len = int(seg_len)
         self.prior = bool(prior)
         self.nclass = int(nclass)
+        self.ctx2d, self.tile = bool(ctx2d), (int(tile[0]), int(tile[1]))
+        if self.ctx2d and self.ORDER != 0:
+            raise NotImplementedError("the 2-D context takes the order's place: order 0")
+
+    @staticmethod
+    def _symbols(img) -> np.ndarray:
+        img = np.asarray(img)
+        if img.size and (img.min() < 0 or img.max() > 255):
+            raise ValueError("CBAAC codes byte symbols (0..255)")
+        return img
+
+    def decompress(self, data, fn=None) -> np.ndarray:
+        """One reader for versions 1-4, dispatched on the version field."""
+        if isinstance(data, io.BytesIO):
+            data = data.getvalue()
+        data = bytes(data)
+        try:
+            tiles = container_version(data) == VERSION_2D
+            fields = _parse2d(data) if tiles else _parse(data)
+        except (ValueError, struct.error):
+            return np.zeros((10, 10), np.uint8)      # CBAAC.py:101-102
+        return self._decode_tiles(*fields) if tiles else self._decode_segments(*fields)
+
+
+class HostTiledCBAACCodec(_Container):
+    """TiledCBAACCodec on the CPU: the serial host coders run segment by
+    segment (versions 1-3) or over the frame's tiles (version 4,
+    vcf_cbaac2d_*), writing the bytes the GPU writes.  For machines without a
+    GPU, and what the GPU coder is compared against."""
+
+    def compress(self, img: np.ndarray, fn=None) -> io.BytesIO:
+        img = self._symbols(img)
+        k = np.ascontiguousarray(img, np.uint8)
+        if self.ctx2d:
+            th, tw = self.tile
+            priors = prior2d_of(k, th, tw, self.nclass)
+            tiles = host_tiles2d(k, priors, th, tw, self.nclass)
+            data = pack2d(img.shape, th, tw, self.nclass, priors, [len(t) for t in tiles], b"".join(tiles))
+        else:
+            prior = prior_of(k, self.nclass, self.seg_len) if self.prior else None
+            segs = (host_segments_prior(k, prior, self.seg_len, self.ORDER) if self.prior else
+                    host_segments(k, self.ORDER, self.seg_len))
+            data = pack(img.shape, self.ORDER, self.seg_len, [len(s) for s in segs], b"".join(segs), prior)
+        b = io.BytesIO(data)
+        b.seek(0)
+        return b
+
+    def _decode_tiles(self, shape, th, tw, nclass, priors, tile_bytes, payload):
+        return host_decode2d(payload, tile_bytes, shape, priors, th, tw, nclass)
+
+    def _decode_segments(self, shape, order, seg_len, seg_bytes, payload, prior):
+        from .cbaac import decode_symbols
+        n = int(np.prod(shape))
+        out = np.empty(n, np.uint8)
+        ends = np.cumsum(seg_bytes)
+        for i, (nb, e) in enumerate(zip(seg_bytes, ends)):
+            part = payload[int(e - nb):int(e)]
+            m = min(seg_len, n - i * seg_len)
+            if prior is None:
+                out[i * seg_len:i * seg_len + m] = decode_symbols(part, m, order)
+            else:
+                row = prior[i * prior.shape[0] // len(seg_bytes)] if prior.ndim == 2 else prior
+                out[i * seg_len:i * seg_len + m] = host_decode_prior(part, m, row, order)
+        return out.reshape(shape)
+
+
+class TiledCBAACCodec(_Container):
+    """The entropy-codec surface of CBAAC.CoDec (compress/decompress,
+    file_extension; CBAAC.py:72-156) over the tiled GPU coder."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
         self._coder = None
         self._make = threading.Lock()
 
     @property
-    def coder(self) -> TiledCoder:
+    def coder(self):
         with self._make:
             if self._coder is None:
-                self._coder = TiledCoder(self.ORDER, self.seg_len, prior=self.prior, nclass=self.nclass)
+                if self.ctx2d:
+                    self._coder = Tiled2DCoder(self.tile, self.nclass)
+                else:
+                    self._coder = TiledCoder(self.ORDER, self.seg_len, prior=self.prior, nclass=self.nclass)
             return self._coder
 
     def compress(self, img: np.ndarray, fn=None) -> io.BytesIO:
-        img = np.asarray(img)
+        img = self._symbols(img)
         flat = img.ravel()
-        if flat.size and (flat.min() < 0 or flat.max() > 255):
-            raise ValueError("CBAAC codes byte symbols (0..255)")
         coder = self.coder
+        if self.ctx2d:
+            with coder.lock:    # last_prior belongs to this call's encode
+                tiles, payload = coder.encode(img)
+                b = io.BytesIO(pack2d(img.shape, *self.tile, self.nclass, coder.last_prior, tiles, payload))
+            b.seek(0)
+            return b
         with coder.lock:    # last_prior belongs to this call's encode
             sizes, payload = coder.encode(flat.astype(np.uint8))
             prior = coder.last_prior if self.prior else None
@@ -531,23 +854,26 @@ class TiledCBAACCodec:
         n = int(np.prod(shape))
         coder = self.coder
         with coder.lock:
-            sizes, payload = coder.encode_device(k, n, offset)
-            prior = coder.last_prior if self.prior else None
-        b = io.BytesIO(pack(tuple(shape), self.ORDER, self.seg_len, sizes, payload, prior))
+            if self.ctx2d:
+                tiles, payload = coder.encode_device(k, shape, offset)
+                data = pack2d(tuple(shape), *self.tile, self.nclass, coder.last_prior, tiles, payload)
+            else:
+                sizes, payload = coder.encode_device(k, n, offset)
+                data = pack(tuple(shape), self.ORDER, self.seg_len, sizes, payload,
+                            coder.last_prior if self.prior else None)
+        b = io.BytesIO(data)
         b.seek(0)
         return b
 
-    def decompress(self, data, fn=None) -> np.ndarray:
-        if isinstance(data, io.BytesIO):
-            data = data.getvalue()
-        data = bytes(data)
-        try:
-            shape, order, seg_len, seg_bytes, payload, prior = _parse(data)
-        except (ValueError, struct.error):
-            return np.zeros((10, 10), np.uint8)      # CBAAC.py:101-102
-        coder = self.coder if (order, seg_len) == (self.ORDER, self.seg_len) else TiledCoder(order, seg_len)
+    def _decode_segments(self, shape, order, seg_len, seg_bytes, payload, prior):
+        mine = not self.ctx2d and (order, seg_len) == (self.ORDER, self.seg_len)
+        coder = self.coder if mine else TiledCoder(order, seg_len)
         n = int(np.prod(shape))
         return coder.decode(payload, seg_bytes, n, prior).reshape(shape)
+
+    def _decode_tiles(self, shape, th, tw, nclass, priors, tile_bytes, payload):
+        coder = self.coder if self.ctx2d and (th, tw) == self.tile else Tiled2DCoder((th, tw), nclass)
+        return coder.decode(payload, tile_bytes, shape, priors, nclass)
 
 
 def host_segments(sym: np.ndarray, order: int = 0, seg_len: int = DEFAULT_SEG):
@@ -607,4 +933,50 @@ def host_decode_prior(data: bytes, n: int, prior, order: int = 0) -> np.ndarray:
     buf = np.frombuffer(data, np.uint8)
     L.call("vcf_cbaac_decode_prior", buf.ctypes.data if buf.size else None, buf.size, n, order, prior.ctypes.data,
            out.ctypes.data)
+    return out
+
+
+def prior2d_of(img: np.ndarray, th: int = TILE_2D[0], tw: int = TILE_2D[1], nclass: int = PRIOR_CLASSES) -> np.ndarray:
+    """Version 4's (nclass * 16, 256) prior rows of a frame on the host
+    (vcf_cbaac2d_prior; what vcf_cbaac_tiled2d_prior_frames computes on the GPU)."""
+    img = np.ascontiguousarray(img, np.uint8)
+    H, W, C = frame_dims(img.shape)
+    rows = np.empty((int(nclass) * NCTX_2D, 256), np.uint16)
+    L.call("vcf_cbaac2d_prior", img.ctypes.data, H, W, C, int(th), int(tw), int(nclass), rows.ctypes.data)
+    return rows
+
+
+def host_tiles2d(img: np.ndarray, priors, th: int = TILE_2D[0], tw: int = TILE_2D[1],
+                 nclass: int = PRIOR_CLASSES) -> list:
+    """The host serial coder (vcf_cbaac2d_encode) over a frame -> its tiles'
+    bytes, in tile order: what each tile of a version-4 stream must equal."""
+    import ctypes
+    img = np.ascontiguousarray(img, np.uint8)
+    H, W, C = frame_dims(img.shape)
+    priors = check_rows2d(priors, nclass)
+    nt = n_tiles2d(img.shape, th, tw)
+    cap = nt * int(L.lib().vcf_cbaac_bound(int(th) * int(tw)))
+    out = np.empty(max(cap, 1), np.uint8)
+    sizes = np.zeros(max(nt, 1), np.int64)
+    total = ctypes.c_int64()
+    L.call("vcf_cbaac2d_encode", img.ctypes.data, H, W, C, int(th), int(tw), int(nclass), priors.ctypes.data,
+           out.ctypes.data, cap, sizes.ctypes.data, ctypes.byref(total))
+    ends = np.cumsum(sizes[:nt])
+    return [out[int(e - s):int(e)].tobytes() for s, e in zip(sizes[:nt], ends)]
+
+
+def host_decode2d(payload: bytes, tile_bytes, shape, priors, th: int = TILE_2D[0], tw: int = TILE_2D[1],
+                  nclass: int = PRIOR_CLASSES) -> np.ndarray:
+    """vcf_cbaac2d_decode: a version-4 payload back to the frame, on the host."""
+    H, W, C = frame_dims(shape)
+    priors = check_rows2d(priors, nclass)
+    tile_bytes = np.asarray(tile_bytes, np.int64)
+    offs = np.zeros(tile_bytes.size + 1, np.int64)
+    np.cumsum(tile_bytes, out=offs[1:])
+    if tile_bytes.size != n_tiles2d(shape, th, tw) or int(offs[-1]) != len(payload):
+        raise ValueError("tile sizes do not match the frame or the payload")
+    buf = np.frombuffer(payload, np.uint8)
+    out = np.empty(tuple(int(s) for s in shape), np.uint8)
+    L.call("vcf_cbaac2d_decode", buf.ctypes.data if buf.size else None, offs.ctypes.data, H, W, C, int(th), int(tw),
+           int(nclass), priors.ctypes.data, out.ctypes.data)
     return out
