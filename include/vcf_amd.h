@@ -126,6 +126,15 @@ int vcf_dct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t
 int vcf_mdct_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp, int32_t *Wp, int32_t *pad_top,
                           int32_t *pad_left);
 
+/* The launch plan vcf_mdct_dz_encode (decode = 0) or vcf_mdct_dz_decode (decode
+ * != 0) uses for this shape, block size and flags: the workgroup's tile in
+ * blocks (decode: output segments) TX x TY, the LDS class (0, 1, 2: 40, 80,
+ * 156 KiB per workgroup) and the number of tiles each way.  Computed by the
+ * code the launches call.  Host only; the shape, block size and flag rules of
+ * vcf_mdct_dz_encode. */
+int vcf_mdct_tile_plan(int32_t H, int32_t W, int32_t block_size, uint32_t flags, int32_t decode, int32_t *TX,
+                       int32_t *TY, int32_t *lds_class, int32_t *tiles_x, int32_t *tiles_y);
+
 /* 2D-MDCT.py encode_fn :498-582 between the image read and the entropy codec:
  * n_frames RGB frames (H x W x 3 u8) -> coefficient frames (Hp x Wp x 3 u8 of
  * vcf_mdct_padded_shape): centred symmetric pad, -128, YCoCg, Malvar's lapped

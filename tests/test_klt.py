@@ -1,7 +1,9 @@
 """The 2D-KLT codec without a GPU: the numpy restatement (tests/klt_restated.py)
 against the reference's own fixtures (tests/golden/klt_*.npz,
 make_golden_klt.py), the host-only ABI, argument validation before any device
-work, the refusals and the command-line surface."""
+work, the refusals, the command-line surface, and the conditions under which
+the block-size sweep of tests/test_klt_sweep_gpu.py means something
+(tests/klt_sweep_cases.py)."""
 import ctypes
 import json
 import os
@@ -12,6 +14,7 @@ import pytest
 from conftest import GOLDEN
 
 import klt_restated as K
+import klt_sweep_cases as S
 import vcf_amd._lib as L
 from test_mdct import CAP
 
@@ -134,6 +137,49 @@ def test_summation_orders_stay_within_the_cap(B):
     w32 = w64.astype(np.float32)
     da, db = K.decode(a["k"], H, W, w32, B, 32, 0, "fwd"), K.decode(a["k"], H, W, w32, B, 32, 0, "rev")
     assert np.count_nonzero(da["rgb"] != db["rgb"]) <= CAP * da["rgb"].size
+
+
+# ---- the block-size sweep (tests/klt_sweep_cases.py): what keeps it honest ----------
+@pytest.mark.parametrize("name", S.ENCODE_IDS)
+def test_sweep_encode_cases_do_not_depend_on_the_summation_order(name):
+    """On the sweep's frame CAP * size is about 1 position, so the reference alone must be exact:
+    both accumulation orders give the same indices and the same pixels.  At Q = 1 the case is there
+    for the encoder's wrap to u8: at least 1 % of the indices leave 0..255."""
+    case = S.by_name(name)
+    a = S.encoded(name)
+    assert np.array_equal(a["k"], S.encode(case, "rev")["k"])
+    assert np.array_equal(S.decoded(name)["rgb"], S.decode(case, a["k"], "rev")["rgb"])
+    wrapped = np.mean((a["k32"] < 0) | (a["k32"] > 255))
+    print(f"{name}: {wrapped:.4f} of the indices wrap")
+    if case["Q"] == 1:
+        assert wrapped >= 0.01
+        assert not np.array_equal(a["k"], np.clip(a["k32"], 0, 255).astype(np.uint8))
+
+
+@pytest.mark.parametrize("name", S.RAW_IDS)
+def test_sweep_raw_cases_are_fit_to_decode(name):
+    """Index frames no encoder writes: the decode does not depend on the summation order and at most
+    half of the pixels are clipped."""
+    case = S.by_name(name)
+    k = S.raw_k(name)
+    d = S.decoded(name)
+    assert np.array_equal(d["rgb"], S.decode(case, k, "rev")["rgb"])
+    saturated = np.mean((d["rgb"] == 0) | (d["rgb"] == 255))
+    wrapping = np.count_nonzero(np.abs(case["Q"] * (k.astype(np.int64) - 128)) > 32767)
+    print(f"{name}: {saturated:.4f} of the pixels at 0 or 255, {wrapping} indices wrap in int16")
+    assert saturated <= 0.5
+    if case["Q"] == 1:
+        assert len(np.unique(k)) == 256
+    else:
+        assert wrapping >= 1
+
+
+def test_sweep_weights_are_orthonormal():
+    for B in S.SWEEP_B:
+        w = S.weights(B)
+        assert w.shape == (3, B * B, B * B) and w.dtype == np.float64
+        assert np.max(np.abs(w @ w.transpose(0, 2, 1) - np.eye(B * B))) <= 1e-12
+        assert S.weights32(B).dtype == np.float32
 
 
 def test_restatement_refuses_what_the_reference_cannot_do():

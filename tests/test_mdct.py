@@ -1,7 +1,9 @@
 """The lapped 2D-MDCT codec without a GPU: the numpy restatement
 (tests/mdct_restated.py) against the reference's own fixtures
 (tests/golden/mdct_*.npz, make_golden_mdct.py), the host-only ABI, argument
-validation before any device work, and the command-line surface."""
+validation before any device work, the command-line surface, and the
+conditions under which the block-size sweep of tests/test_mdct_sweep_gpu.py
+means something (tests/mdct_sweep_cases.py)."""
 import ctypes
 import json
 import os
@@ -12,6 +14,7 @@ import pytest
 from conftest import GOLDEN
 
 import mdct_restated as M
+import mdct_sweep_cases as S
 import vcf_amd._lib as L
 
 CAP = 1e-5   # positions that may depend on the float64 summation order, per case
@@ -105,6 +108,100 @@ def test_summation_orders_stay_within_the_cap(B):
     H, W = rgb.shape[:2]
     da, db = M.decode(a["k"], H, W, B, 32, 0, "fwd"), M.decode(a["k"], H, W, B, 32, 0, "rev")
     assert np.count_nonzero(da["rgb"] != db["rgb"]) <= CAP * da["rgb"].size
+
+
+# ---- the block-size sweep (tests/mdct_sweep_cases.py): what keeps it honest --------
+def _plan(case, decode):
+    """(TX, TY, lds_class, tiles_x, tiles_y) of the launch, from the library itself."""
+    import vcf_amd.mdct as G
+    H, W = case["shape"]
+    return G.tile_plan(H, W, case["B"], case["flags"], decode)
+
+
+@pytest.mark.parametrize("name", S.ENCODE_IDS)
+def test_sweep_encode_cases_do_not_depend_on_the_summation_order(name):
+    """At these sizes CAP * size is 1 to 4 positions, so the GPU comparison is all but exact and the
+    reference alone must be exact: both accumulation orders give the same indices and pixels."""
+    case = S.by_name(name)
+    a = S.encoded(name)
+    assert np.array_equal(a["k"], S.encode(case, "rev")["k"])
+    assert np.array_equal(S.decoded(name)["rgb"], S.decode(case, a["k"], "rev")["rgb"])
+
+
+@pytest.mark.parametrize("name", S.RAW_IDS)
+def test_sweep_raw_cases_are_fit_to_decode(name):
+    """Conditions on the inputs no encoder writes: the decode does not depend on the summation order,
+    at most half of the pixels are clipped, and a wrap case does wrap."""
+    case = S.by_name(name)
+    k = S.raw_k(name)
+    d = S.decoded(name)
+    assert np.array_equal(d["rgb"], S.decode(case, k, "rev")["rgb"])
+    saturated = np.mean((d["rgb"] == 0) | (d["rgb"] == 255))
+    wrapping = np.count_nonzero(np.abs(case["Q"] * (k.astype(np.int64) - 128)) > 32767)
+    print(f"{name}: {saturated:.4f} of the pixels at 0 or 255, {wrapping} wrapping coefficients")
+    assert saturated <= 0.5
+    if case["kind"] == "wrap":
+        assert wrapping >= 100
+        y = (case["Q"] * (k.astype(np.int32) - 128)).astype(np.int16)
+        assert np.max(np.abs(y.astype(np.int32))) <= case["bound"]
+    else:
+        assert case["Q"] == 1 and len(np.unique(k)) == case["hi"] - case["lo"] + 1
+
+
+def _reachable(flags, decode):
+    """The LDS classes the launch can pick at all: over every block size the flags allow and frames
+    from one block to 4K."""
+    import vcf_amd.mdct as G
+    sizes = (1, 9, 24, 61, 97, 150, 256, 480, 1080, 2160, 3840)
+    return {G.tile_plan(H, W, B, flags, decode)[2]
+            for B in ((8,) if flags & M.PERCEPTUAL else range(2, 65)) for H in sizes for W in sizes}
+
+
+def test_sweep_reaches_every_lds_class():
+    """What the sweep launches, from vcf_mdct_tile_plan: encode, decode and decode with -p (float
+    coefficients in LDS) each meet every LDS class they can reach; class 2 runs with tiles of more
+    than one block, at least 2 each way; every class, and every case whose tiles can be, has a
+    partial last tile.  Retuning pick_tile so that the sweep stops reaching a class fails here."""
+    met = {("encode", 0): {}, ("decode", 0): {}, ("decode", M.PERCEPTUAL): {}}
+    for case in S.ENCODE + S.RAW:
+        partial, one_block = False, True
+        for decode in (False, True):
+            if not decode and "kind" in case:
+                continue
+            TX, TY, cls, tx, ty = _plan(case, decode)
+            ex, ey = S.extents(case, decode)
+            part = "x" * bool(ex % TX) + "y" * bool(ey % TY)
+            print(f"{case['name']:>22} {'decode' if decode else 'encode'}: tile {TX}x{TY}, class {cls}, {tx}x{ty} tiles"
+                  f" of {ex}x{ey}" + (f", last one partial in {part}" if part else ""))
+            assert (tx, ty) == ((ex + TX - 1) // TX, (ey + TY - 1) // TY)
+            assert tx * ty > 1 or case["shape"] != S.FRAME
+            partial, one_block = partial or bool(part), one_block and TX * TY == 1
+            key = ("decode", case["flags"] & M.PERCEPTUAL) if decode else ("encode", 0)
+            met[key].setdefault(cls, []).append((TX, TY, tx, ty, part))
+        # a tile of one block is never partial (B = 63, 64); the 1 x 2 and 2 x 1 tiles of B = 40
+        # divide its 8 x 6 blocks and 6 x 4 segments
+        assert partial or one_block or case["name"] in S.WHOLE_TILES, case["name"]
+    for (what, perc), by_class in met.items():
+        assert set(by_class) == _reachable(perc, what == "decode"), (what, perc, sorted(by_class))
+        for cls, plans in by_class.items():
+            assert any(p[4] for p in plans), (what, perc, cls, "no partial last tile")
+    for key, by_class in met.items():
+        assert any(TX * TY > 1 and tx >= 2 and ty >= 2 for TX, TY, tx, ty, _ in by_class[2]), key
+    # the -p decoder, in each of its classes: a seam in y and a partial last tile in y
+    for cls, plans in met[("decode", M.PERCEPTUAL)].items():
+        assert any(ty >= 2 and "y" in part for _, _, _, ty, part in plans), cls
+
+
+def test_tile_plan_errors():
+    v = [ctypes.c_int32() for _ in range(5)]
+    p = [ctypes.byref(x) for x in v]
+    f = L.lib().vcf_mdct_tile_plan
+    assert f(150, 210, 8, 0, 0, *p) == 0 and all(x.value >= 0 for x in v)
+    assert f(0, 210, 8, 0, 0, *p) == L.VCF_ERR_INVALID
+    assert f(150, 210, 65, 0, 1, *p) == L.VCF_ERR_UNSUPPORTED
+    assert f(150, 210, 16, 2, 1, *p) == L.VCF_ERR_UNSUPPORTED   # -p away from B = 8, as the launches
+    assert f(150, 210, 8, 8, 0, *p) == L.VCF_ERR_INVALID
+    assert f(150, 210, 8, 0, 0, None, None, None, None, None) == L.VCF_ERR_INVALID
 
 
 # ---- host-only ABI ---------------------------------------------------------

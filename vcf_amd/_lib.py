@@ -95,6 +95,7 @@ SIGNATURES = {
     "vcf_dct_raw_encode": [_P, _I64, _I32, _I32, _I32, _U32, _P, _P],
     "vcf_dct_raw_decode": [_P, _I64, _I32, _I32, _I32, _U32, _P, _P],
     "vcf_mdct_padded_shape": [_I32, _I32, _I32, _PI32, _PI32, _PI32, _PI32],
+    "vcf_mdct_tile_plan": [_I32, _I32, _I32, _U32, _I32, _PI32, _PI32, _PI32, _PI32, _PI32],
     "vcf_mdct_dz_encode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P],
     "vcf_mdct_dz_decode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P],
     "vcf_klt_padded_shape": [_I32, _I32, _I32, _PI32, _PI32, _PI32, _PI32],

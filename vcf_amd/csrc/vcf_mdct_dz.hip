@@ -410,6 +410,18 @@ void make_geom(int32_t H, int32_t W, int32_t B, MdctGeom &g)
     g.k_stride = (long long)g.Hp * g.Wp * 3;
 }
 
+// the tile and LDS class of one launch: over the blocks on encode, over the segments that meet the
+// crop on decode
+int plan_tiles(MdctGeom &g, bool decode, bool perc)
+{
+    int cls;
+    const int ext_x = decode ? g.nsx : g.nbx, ext_y = decode ? g.nsy : g.nby;
+    pick_tile(g.N, ext_x, ext_y, decode, perc, g.TX, g.TY, cls);
+    g.tiles_x = (ext_x + g.TX - 1) / g.TX;
+    g.tiles_y = (ext_y + g.TY - 1) / g.TY;
+    return cls;
+}
+
 float scale_factor(int B)
 {
     // 2D-MDCT.py:412-421, computed in double as there, used as float32
@@ -455,6 +467,17 @@ int device_tables(int N, const double *&tab)
     return VCF_OK;
 }
 
+// what the host-only queries accept
+int check_shape(int32_t H, int32_t W, int32_t B)
+{
+    if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad shape %d x %d", H, W);
+    if (B < kMinB || B > kMaxB)
+        return set_error(VCF_ERR_UNSUPPORTED, "block size %d: the MDCT kernels cover 2 <= B <= 64", B);
+    if ((long long)H + 3LL * B > INT32_MAX || (long long)W + 3LL * B > INT32_MAX)
+        return set_error(VCF_ERR_INVALID, "bad shape %d x %d", H, W);
+    return VCF_OK;
+}
+
 int check_args(const void *a, const void *b, int64_t n_frames, int32_t H, int32_t W, int32_t B, int32_t Q,
                uint32_t flags)
 {
@@ -486,17 +509,32 @@ int vcf_mdct_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp,
                           int32_t *pad_left)
 {
     if (!Hp || !Wp || !pad_top || !pad_left) return set_error(VCF_ERR_INVALID, "null pointer");
-    if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad shape %d x %d", H, W);
-    if (block_size < kMinB || block_size > kMaxB)
-        return set_error(VCF_ERR_UNSUPPORTED, "block size %d: the MDCT kernels cover 2 <= B <= 64", block_size);
-    if ((long long)H + 3LL * block_size > INT32_MAX || (long long)W + 3LL * block_size > INT32_MAX)
-        return set_error(VCF_ERR_INVALID, "bad shape %d x %d", H, W);
+    const int rc = check_shape(H, W, block_size);
+    if (rc != VCF_OK) return rc;
     MdctGeom g;
     make_geom(H, W, block_size, g);
     *Hp = g.Hp;
     *Wp = g.Wp;
     *pad_top = g.top;
     *pad_left = g.left;
+    return VCF_OK;
+}
+
+int vcf_mdct_tile_plan(int32_t H, int32_t W, int32_t block_size, uint32_t flags, int32_t decode, int32_t *TX,
+                       int32_t *TY, int32_t *lds_class, int32_t *tiles_x, int32_t *tiles_y)
+{
+    if (!TX || !TY || !lds_class || !tiles_x || !tiles_y) return set_error(VCF_ERR_INVALID, "null pointer");
+    // no buffers, one frame, Q = 1: the shape, block size and flag rules of the launches
+    int rc = check_shape(H, W, block_size);
+    if (rc == VCF_OK) rc = check_args(&rc, &rc, 1, H, W, block_size, 1, flags);
+    if (rc != VCF_OK) return rc;
+    MdctGeom g;
+    make_geom(H, W, block_size, g);
+    *lds_class = plan_tiles(g, decode != 0, decode != 0 && (flags & VCF_DCT_PERCEPTUAL) != 0);
+    *TX = g.TX;
+    *TY = g.TY;
+    *tiles_x = g.tiles_x;
+    *tiles_y = g.tiles_y;
     return VCF_OK;
 }
 
@@ -508,10 +546,7 @@ int vcf_mdct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int3
     if (n_frames == 0) return VCF_OK;
     MdctGeom g;
     make_geom(H, W, block_size, g);
-    int cls;
-    pick_tile(g.N, g.nbx, g.nby, false, false, g.TX, g.TY, cls);
-    g.tiles_x = (g.nbx + g.TX - 1) / g.TX;
-    g.tiles_y = (g.nby + g.TY - 1) / g.TY;
+    const int cls = plan_tiles(g, false, false);
     const double *tab = nullptr;
     if ((rc = device_tables(g.N, tab)) != VCF_OK) return rc;
     const float scale = scale_factor(g.N);
@@ -542,10 +577,7 @@ int vcf_mdct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_
     MdctGeom g;
     make_geom(H, W, block_size, g);
     const bool perc = (flags & VCF_DCT_PERCEPTUAL) != 0;
-    int cls;
-    pick_tile(g.N, g.nsx, g.nsy, true, perc, g.TX, g.TY, cls);
-    g.tiles_x = (g.nsx + g.TX - 1) / g.TX;
-    g.tiles_y = (g.nsy + g.TY - 1) / g.TY;
+    const int cls = plan_tiles(g, true, perc);
     const double *tab = nullptr;
     if ((rc = device_tables(g.N, tab)) != VCF_OK) return rc;
     const float scale = scale_factor(g.N);

@@ -17,7 +17,7 @@ from ._blockio import check_input, flags_from, frames_u8, output, round_trip
 from ._lib import VCF_DCT_NO_SUBBANDS, VCF_DCT_PERCEPTUAL, call
 from .device import DeviceBuffer, _h
 
-__all__ = ["padded_shape", "shape_bin", "flags_from", "encode_device", "decode_device", "encode", "decode",
+__all__ = ["padded_shape", "tile_plan", "shape_bin", "flags_from", "encode_device", "decode_device", "encode", "decode",
            "VCF_DCT_NO_SUBBANDS", "VCF_DCT_PERCEPTUAL"]
 
 
@@ -25,6 +25,14 @@ def padded_shape(H: int, W: int, block_size: int = 8):
     """(Hp, Wp, pad_top, pad_left) of 2D-MDCT.py:446-476."""
     v = [ctypes.c_int32() for _ in range(4)]
     call("vcf_mdct_padded_shape", H, W, block_size, *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def tile_plan(H: int, W: int, block_size: int = 8, flags: int = 0, decode: bool = False):
+    """(TX, TY, lds_class, tiles_x, tiles_y) of the encode (or decode) launch: the tile in blocks
+    (decode: segments), the LDS class 0..2 and the tiles each way.  Host only."""
+    v = [ctypes.c_int32() for _ in range(5)]
+    call("vcf_mdct_tile_plan", H, W, block_size, flags, int(bool(decode)), *[ctypes.byref(x) for x in v])
     return tuple(x.value for x in v)
 
 
