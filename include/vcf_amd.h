@@ -561,6 +561,42 @@ int vcf_cbaac_tiled2d_encode_frames(const uint8_t *sym_dev, int64_t n_frames, in
 int vcf_cbaac_tiled2d_decode_frames(const uint8_t *in_dev, const int64_t *tile_offsets_dev, int64_t n_frames, int64_t H,
                                     int64_t W, int64_t C, const uint16_t *priors_dev, int32_t nclass, int64_t th,
                                     int64_t tw, uint8_t *sym_dev, int64_t out_frame_stride, void *stream);
+/* GPU, plane lists: n_arrays (1 .. 2^20) arrays of different sizes anywhere
+ * in one device buffer of buf_bytes bytes (the packed subbands of a batch of
+ * 2D-DWT frames), every 64 x 64 tile of every array in one launch per stage.
+ * Array a is H x W x C symbols (H, W, C >= 1, channels interleaved) from byte
+ * `base`; tile0 = the tiles of the arrays before it, so the launch's n_tiles
+ * tiles are numbered array by array, each array's as the frame entry points
+ * number a frame's.  Array a's code-stream is, byte for byte, what the frame
+ * entry points (and the host coder) give for that array alone: its prior rows
+ * are rows a * nclass * 16 .. of priors_dev (n_arrays x nclass x 16 x 256
+ * uint16, 8-byte aligned; hist_dev as many uint32), its tiles' bytes
+ * out_dev[offset(tile0) .. offset(tile0 + tiles)), the packed tiles of all
+ * arrays back to back; tile_bytes_dev takes the n_tiles byte counts and their
+ * total.  desc_host and desc_dev hold the same n_arrays descriptors: the host
+ * copy is checked (sizes, tile0, every array inside buf_bytes) before
+ * anything is launched, the kernels read the device copy.  Decode:
+ * tile_offsets_dev = n_tiles + 1 offsets into in_dev; array a's symbols are
+ * written at its base. */
+typedef struct vcf_plane_desc {
+    int64_t base;
+    int32_t H, W, C;
+    int32_t tile0;
+} vcf_plane_desc;
+int64_t vcf_cbaac_tiled2d_planes_workspace(int64_t n_tiles, int64_t th, int64_t tw);
+int64_t vcf_cbaac_tiled2d_planes_bound(int64_t n_tiles, int64_t th, int64_t tw);
+int vcf_cbaac_tiled2d_prior_planes(const uint8_t *buf_dev, int64_t buf_bytes, const vcf_plane_desc *desc_host,
+                                   const vcf_plane_desc *desc_dev, int64_t n_arrays, int64_t n_tiles, int64_t th,
+                                   int64_t tw, int32_t nclass, uint16_t *priors_dev, uint32_t *hist_dev, void *stream);
+int vcf_cbaac_tiled2d_encode_planes(const uint8_t *buf_dev, int64_t buf_bytes, const vcf_plane_desc *desc_host,
+                                    const vcf_plane_desc *desc_dev, int64_t n_arrays, int64_t n_tiles,
+                                    const uint16_t *priors_dev, int32_t nclass, int64_t th, int64_t tw,
+                                    uint8_t *out_dev, int64_t out_capacity, int64_t *tile_bytes_dev, void *ws_dev,
+                                    void *stream);
+int vcf_cbaac_tiled2d_decode_planes(const uint8_t *in_dev, const int64_t *tile_offsets_dev,
+                                    const vcf_plane_desc *desc_host, const vcf_plane_desc *desc_dev, int64_t n_arrays,
+                                    int64_t n_tiles, const uint16_t *priors_dev, int32_t nclass, int64_t th, int64_t tw,
+                                    uint8_t *buf_dev, int64_t buf_bytes, void *stream);
 
 /* ---- CBAHC entropy codec (CBAHC.py), host code --------------------------------- */
 

@@ -190,6 +190,11 @@ SIGNATURES = {
     "vcf_cbaac_tiled2d_prior_frames": [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _P, _P, _P],
     "vcf_cbaac_tiled2d_encode_frames": [_P, _I64, _I64, _I64, _I64, _I64, _P, _I32, _I64, _I64, _P, _I64, _P, _P, _P],
     "vcf_cbaac_tiled2d_decode_frames": [_P, _P, _I64, _I64, _I64, _I64, _P, _I32, _I64, _I64, _P, _I64, _P],
+    "vcf_cbaac_tiled2d_planes_workspace": [_I64, _I64, _I64],
+    "vcf_cbaac_tiled2d_planes_bound": [_I64, _I64, _I64],
+    "vcf_cbaac_tiled2d_prior_planes": [_P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I32, _P, _P, _P],
+    "vcf_cbaac_tiled2d_encode_planes": [_P, _I64, _P, _P, _I64, _I64, _P, _I32, _I64, _I64, _P, _I64, _P, _P, _P],
+    "vcf_cbaac_tiled2d_decode_planes": [_P, _P, _P, _P, _I64, _I64, _P, _I32, _I64, _I64, _P, _I64, _P],
     "vcf_leb128_encode_rows": [_P, _I64, _I64, _P, _I64, _P],
     "vcf_prior_rows_sparse": [_P, _I64, _I32, _P, _I64, _P],
     "vcf_comm_unique_id": [_P, _SZ],
@@ -267,7 +272,8 @@ def lib():
             L.vcf_png_encode_bound.restype = ctypes.c_int64
             for name in ("vcf_cbaac_tiled_segments", "vcf_cbaac_tiled_workspace", "vcf_cbaac_tiled_bound",
                          "vcf_cbaac_tiled_frames_workspace", "vcf_cbaac2d_tiles", "vcf_cbaac_tiled2d_tiles",
-                         "vcf_cbaac_tiled2d_workspace", "vcf_cbaac_tiled2d_bound", "vcf_zlib_bound", "vcf_zlib_workspace",
+                         "vcf_cbaac_tiled2d_workspace", "vcf_cbaac_tiled2d_bound", "vcf_cbaac_tiled2d_planes_workspace",
+                         "vcf_cbaac_tiled2d_planes_bound", "vcf_zlib_bound", "vcf_zlib_workspace",
                          "vcf_zlib_strip_count"):
                 getattr(L, name).restype = ctypes.c_int64
             _lib = L

@@ -1196,29 +1196,26 @@ __device__ __forceinline__ void lds2d_init(Lds2d &L, const uint16_t *__restrict_
     __syncthreads();
 }
 
-__global__ __launch_bounds__(64) void cbaac2d_encode_kernel(const uint8_t *__restrict__ sym, Geom2d g,
-                                                            uint32_t *__restrict__ slots, int64_t slot_words,
-                                                            int64_t *__restrict__ tile_bits,
-                                                            const uint16_t *__restrict__ priors, Frames fr)
+// one tile: its symbols from src (the tile's first symbol; rows rs apart,
+// symbols C apart), its models from the 16 prior rows at `rows`, its bits into
+// `slot`, their count to *bits_out
+__device__ __forceinline__ void cbaac2d_encode_tile(Lds2d &L, const uint8_t *__restrict__ src, int64_t rs, int64_t C,
+                                                    const Tile2d &tl, const uint16_t *__restrict__ rows,
+                                                    uint32_t *__restrict__ slot, int64_t *__restrict__ bits_out)
 {
-    __shared__ Lds2d L;
-    const int64_t f = blockIdx.y, t = blockIdx.x, per = g.ty * g.tx, nt = g.C * per;
     const uint32_t lane = threadIdx.x;
-    const Tile2d tl = tile2d(g, t);
-    const uint8_t *src = sym + f * fr.sym_stride + tl.base;
-    const int64_t rs = g.W * g.C;
     Model m;
-    lds2d_init(L, priors + f * fr.prior_stride + ((tl.in_plane * fr.nclass) / per) * (kCtx2d * 256), lane, m);
+    lds2d_init(L, rows, lane, m);
     uint32_t ctx = 0;
 
     BitWriter w;
-    w.out = slots + (f * nt + t) * slot_words;
+    w.out = slot;
     Encoder e;
     for (int32_t y = 0; y < tl.h; ++y) {
         uint8_t *cur = L.row[y & 1];
         const uint8_t *up = L.row[(y & 1) ^ 1];
         __syncthreads();   // row y - 2 has been read
-        for (int32_t x = (int32_t)lane; x < tl.w; x += 64) cur[x] = src[y * rs + (int64_t)x * g.C];
+        for (int32_t x = (int32_t)lane; x < tl.w; x += 64) cur[x] = src[y * rs + (int64_t)x * C];
         __syncthreads();
         uint32_t wn = 0;
         for (int32_t x4 = 0; x4 < tl.w; x4 += 4) {
@@ -1244,7 +1241,69 @@ __global__ __launch_bounds__(64) void cbaac2d_encode_kernel(const uint8_t *__res
     }
     e.flush(w, lane);
     const uint64_t bits = w.finish(lane);
-    if (lane == 0) tile_bits[f * nt + t] = (int64_t)bits;
+    if (lane == 0) *bits_out = (int64_t)bits;
+}
+
+__global__ __launch_bounds__(64) void cbaac2d_encode_kernel(const uint8_t *__restrict__ sym, Geom2d g,
+                                                            uint32_t *__restrict__ slots, int64_t slot_words,
+                                                            int64_t *__restrict__ tile_bits,
+                                                            const uint16_t *__restrict__ priors, Frames fr)
+{
+    __shared__ Lds2d L;
+    const int64_t f = blockIdx.y, t = blockIdx.x, per = g.ty * g.tx, nt = g.C * per;
+    const Tile2d tl = tile2d(g, t);
+    cbaac2d_encode_tile(L, sym + f * fr.sym_stride + tl.base, g.W * g.C, g.C, tl,
+                        priors + f * fr.prior_stride + ((tl.in_plane * fr.nclass) / per) * (kCtx2d * 256),
+                        slots + (f * nt + t) * slot_words, tile_bits + f * nt + t);
+}
+
+// ---- plane lists: arrays of different sizes anywhere in one buffer, one launch ----
+// Array a of the list is vcf_plane_desc a: H x W x C symbols (channels
+// interleaved) from byte `base` of the buffer, its tiles numbered tile0 ..
+// tile0 + tiles - 1 in the launch's one list of tiles (slots, bit counts and
+// offsets are indexed by that number; array a's prior rows are rows
+// a * nclass * 16 ...).  A wave finds its array by bisection over tile0
+// (scalar loads, once per wave) and then codes its tile exactly as the frame
+// kernels do: same device code, same LDS (8768 B, 18 waves per CU).
+struct Plane2d {
+    int64_t a, local;   // the array, the tile's number in it
+    const uint8_t *base;
+    Geom2d g;
+};
+
+__device__ __forceinline__ Plane2d plane2d(const vcf_plane_desc *__restrict__ desc, int32_t n_arrays, int64_t t,
+                                           const uint8_t *buf, int64_t th, int64_t tw)
+{
+    int32_t lo = 0, hi = n_arrays - 1;      // the last array whose tile0 <= t
+    while (lo < hi) {
+        const int32_t mid = (lo + hi + 1) >> 1;
+        if ((int64_t)desc[mid].tile0 <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    const vcf_plane_desc d = desc[lo];
+    Plane2d p;
+    p.a = lo;
+    p.local = t - d.tile0;
+    p.base = buf + d.base;
+    p.g = {d.H, d.W, d.C, th, tw, (d.H + th - 1) / th, (d.W + tw - 1) / tw};
+    return p;
+}
+
+__global__ __launch_bounds__(64) void cbaac2d_encode_planes_kernel(const uint8_t *__restrict__ buf,
+                                                                   const vcf_plane_desc *__restrict__ desc,
+                                                                   int32_t n_arrays, int64_t th, int64_t tw,
+                                                                   uint32_t *__restrict__ slots, int64_t slot_words,
+                                                                   int64_t *__restrict__ tile_bits,
+                                                                   const uint16_t *__restrict__ priors, int32_t nclass)
+{
+    __shared__ Lds2d L;
+    const int64_t t = blockIdx.x;
+    const Plane2d p = plane2d(desc, n_arrays, t, buf, th, tw);
+    const Tile2d tl = tile2d(p.g, p.local);
+    const int64_t per = p.g.ty * p.g.tx;
+    cbaac2d_encode_tile(L, p.base + tl.base, p.g.W * p.g.C, p.g.C, tl,
+                        priors + (p.a * nclass + (tl.in_plane * nclass) / per) * (kCtx2d * 256),
+                        slots + t * slot_words, tile_bits + t);
 }
 
 // one symbol of the A8 decoder with model m (the body of cbaac_tiled_decode_kernel's loop)
@@ -1286,25 +1345,19 @@ __device__ __forceinline__ uint32_t decode_step(Model &m, BitReader &br, uint32_
     return s;
 }
 
-__global__ __launch_bounds__(64) void cbaac2d_decode_kernel(const uint8_t *__restrict__ in,
-                                                            const int64_t *__restrict__ offs, Geom2d g,
-                                                            uint8_t *__restrict__ out,
-                                                            const uint16_t *__restrict__ priors, Frames fr)
+// one tile: `nbytes` of bit stream at `bits` -> its symbols to dst (the tile's first symbol)
+__device__ __forceinline__ void cbaac2d_decode_tile(Lds2d &L, const uint8_t *__restrict__ bits, int64_t nbytes,
+                                                    uint8_t *__restrict__ dst, int64_t rs, int64_t C, const Tile2d &tl,
+                                                    const uint16_t *__restrict__ rows)
 {
-    __shared__ Lds2d L;
-    const int64_t f = blockIdx.y, t = blockIdx.x, per = g.ty * g.tx, nt = g.C * per;
     const uint32_t lane = threadIdx.x;
-    const Tile2d tl = tile2d(g, t);
-    uint8_t *dst = out + f * fr.out_stride + tl.base;
-    const int64_t rs = g.W * g.C;
-    offs += f * (nt + 1);
     Model m;
-    lds2d_init(L, priors + f * fr.prior_stride + ((tl.in_plane * fr.nclass) / per) * (kCtx2d * 256), lane, m);
+    lds2d_init(L, rows, lane, m);
     uint32_t ctx = 0;
 
     BitReader br;
-    br.src = in + offs[t];
-    br.nbytes = offs[t + 1] - offs[t];
+    br.src = bits;
+    br.nbytes = nbytes;
     br.start(lane);
     uint32_t low = 0, high = 0xFFFFFFFFu, value = br.get(32, lane);
     for (int32_t y = 0; y < tl.h; ++y) {
@@ -1330,33 +1383,80 @@ __global__ __launch_bounds__(64) void cbaac2d_decode_kernel(const uint8_t *__res
             if (lane == 0) *reinterpret_cast<uint32_t *>(cur + x4) = acc;
         }
         __syncthreads();
-        for (int32_t x = (int32_t)lane; x < tl.w; x += 64) dst[y * rs + (int64_t)x * g.C] = cur[x];
+        for (int32_t x = (int32_t)lane; x < tl.w; x += 64) dst[y * rs + (int64_t)x * C] = cur[x];
     }
+}
+
+__global__ __launch_bounds__(64) void cbaac2d_decode_kernel(const uint8_t *__restrict__ in,
+                                                            const int64_t *__restrict__ offs, Geom2d g,
+                                                            uint8_t *__restrict__ out,
+                                                            const uint16_t *__restrict__ priors, Frames fr)
+{
+    __shared__ Lds2d L;
+    const int64_t f = blockIdx.y, t = blockIdx.x, per = g.ty * g.tx, nt = g.C * per;
+    const Tile2d tl = tile2d(g, t);
+    offs += f * (nt + 1);
+    cbaac2d_decode_tile(L, in + offs[t], offs[t + 1] - offs[t], out + f * fr.out_stride + tl.base, g.W * g.C, g.C, tl,
+                        priors + f * fr.prior_stride + ((tl.in_plane * fr.nclass) / per) * (kCtx2d * 256));
+}
+
+__global__ __launch_bounds__(64) void cbaac2d_decode_planes_kernel(const uint8_t *__restrict__ in,
+                                                                   const int64_t *__restrict__ offs,
+                                                                   const vcf_plane_desc *__restrict__ desc,
+                                                                   int32_t n_arrays, int64_t th, int64_t tw,
+                                                                   uint8_t *__restrict__ buf,
+                                                                   const uint16_t *__restrict__ priors, int32_t nclass)
+{
+    __shared__ Lds2d L;
+    const int64_t t = blockIdx.x;
+    const Plane2d p = plane2d(desc, n_arrays, t, buf, th, tw);
+    const Tile2d tl = tile2d(p.g, p.local);
+    const int64_t per = p.g.ty * p.g.tx;
+    cbaac2d_decode_tile(L, in + offs[t], offs[t + 1] - offs[t], const_cast<uint8_t *>(p.base) + tl.base,
+                        p.g.W * p.g.C, p.g.C, tl,
+                        priors + (p.a * nclass + (tl.in_plane * nclass) / per) * (kCtx2d * 256));
 }
 
 // per-(class, context) histograms: one workgroup per tile (its class is
 // fixed), LDS bins, one global atomic per used bin and tile
+__device__ __forceinline__ void cbaac2d_hist_tile(uint32_t *bins, const uint8_t *__restrict__ src, int64_t rs,
+                                                  int64_t C, const Tile2d &tl, uint32_t *__restrict__ hist)
+{
+    for (int i = threadIdx.x; i < kCtx2d * 256; i += 256) bins[i] = 0;
+    __syncthreads();
+    const int32_t n = tl.h * tl.w;
+    for (int32_t i = threadIdx.x; i < n; i += 256) {
+        const int32_t y = i / tl.w, x = i - y * tl.w;
+        const uint8_t *p = src + y * rs + (int64_t)x * C;
+        const uint32_t wn = x ? mag3(p[-C]) : 0u, nn = y ? mag3(p[-rs]) : 0u;
+        atomicAdd(&bins[(4 * wn + nn) * 256 + *p], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kCtx2d * 256; i += 256)
+        if (bins[i]) atomicAdd(&hist[i], bins[i]);
+}
+
 __global__ __launch_bounds__(256) void cbaac2d_hist_kernel(const uint8_t *__restrict__ sym, Geom2d g, int32_t nclass,
                                                            uint32_t *__restrict__ hist, int64_t sym_stride)
 {
     __shared__ uint32_t bins[kCtx2d * 256];
     const int64_t f = blockIdx.y, per = g.ty * g.tx;
     const Tile2d tl = tile2d(g, blockIdx.x);
-    const uint8_t *src = sym + f * sym_stride + tl.base;
-    const int64_t rs = g.W * g.C;
-    hist += (kCtx2d * 256) * (f * nclass + (tl.in_plane * nclass) / per);
-    for (int i = threadIdx.x; i < kCtx2d * 256; i += 256) bins[i] = 0;
-    __syncthreads();
-    const int32_t n = tl.h * tl.w;
-    for (int32_t i = threadIdx.x; i < n; i += 256) {
-        const int32_t y = i / tl.w, x = i - y * tl.w;
-        const uint8_t *p = src + y * rs + (int64_t)x * g.C;
-        const uint32_t wn = x ? mag3(p[-g.C]) : 0u, nn = y ? mag3(p[-rs]) : 0u;
-        atomicAdd(&bins[(4 * wn + nn) * 256 + *p], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kCtx2d * 256; i += 256)
-        if (bins[i]) atomicAdd(&hist[i], bins[i]);
+    cbaac2d_hist_tile(bins, sym + f * sym_stride + tl.base, g.W * g.C, g.C, tl,
+                      hist + (kCtx2d * 256) * (f * nclass + (tl.in_plane * nclass) / per));
+}
+
+__global__ __launch_bounds__(256) void cbaac2d_hist_planes_kernel(const uint8_t *__restrict__ buf,
+                                                                  const vcf_plane_desc *__restrict__ desc,
+                                                                  int32_t n_arrays, int64_t th, int64_t tw,
+                                                                  int32_t nclass, uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t bins[kCtx2d * 256];
+    const Plane2d p = plane2d(desc, n_arrays, blockIdx.x, buf, th, tw);
+    const Tile2d tl = tile2d(p.g, p.local);
+    const int64_t per = p.g.ty * p.g.tx;
+    cbaac2d_hist_tile(bins, p.base + tl.base, p.g.W * p.g.C, p.g.C, tl,
+                      hist + (kCtx2d * 256) * (p.a * nclass + (tl.in_plane * nclass) / per));
 }
 
 // words per tile slot, even: the int64 tables behind the slots stay 8-byte aligned
@@ -1735,6 +1835,96 @@ int vcf_cbaac_tiled2d_decode_frames(const uint8_t *in_dev, const int64_t *tile_o
     cbaac2d_decode_kernel<<<dim3((unsigned)nt, (unsigned)n_frames), 64, 0, (hipStream_t)stream>>>(
         in_dev, tile_offsets_dev, g, sym_dev, priors_dev, fr);
     return hip_check(hipGetLastError(), "cbaac2d_decode_kernel");
+}
+
+// ---- version 4 over a plane list ---------------------------------------------------------
+// the host copy of the descriptors against the buffer and the tile count: nothing is
+// launched on a list that would read or write outside buf_bytes
+static int check_planes(const vcf_plane_desc *desc_host, const void *desc_dev, int64_t n_arrays, int64_t n_tiles,
+                        int64_t buf_bytes, int64_t th, int64_t tw, int32_t nclass, const void *priors_dev)
+{
+    Geom2d g;
+    if (int s = check_2d(1, 0, 0, 0, th, tw, nclass, priors_dev, g)) return s;
+    if (n_arrays < 1 || n_arrays > (1 << 20)) return set_error(VCF_ERR_INVALID, "n_arrays %lld (1 .. 2^20)", (long long)n_arrays);
+    if (!desc_host || !desc_dev) return set_error(VCF_ERR_INVALID, "null descriptors");
+    if (buf_bytes < 0) return set_error(VCF_ERR_INVALID, "negative buffer size");
+    int64_t tiles = 0;
+    for (int64_t a = 0; a < n_arrays; ++a) {
+        const vcf_plane_desc &d = desc_host[a];
+        if (d.H < 1 || d.W < 1 || d.C < 1) return set_error(VCF_ERR_INVALID, "array %lld: empty", (long long)a);
+        const int64_t hw = (int64_t)d.H * d.W;
+        if (hw > INT64_MAX / d.C) return set_error(VCF_ERR_INVALID, "array %lld: size overflows", (long long)a);
+        if (d.base < 0 || d.base > buf_bytes || hw * d.C > buf_bytes - d.base)
+            return set_error(VCF_ERR_INVALID, "array %lld lies outside the %lld-byte buffer", (long long)a, (long long)buf_bytes);
+        if (d.tile0 != tiles) return set_error(VCF_ERR_INVALID, "array %lld: tile0 %d, %lld tiles before it", (long long)a, d.tile0, (long long)tiles);
+        tiles += vcf_cbaac_tiled2d_tiles(d.H, d.W, d.C, th, tw);
+        if (tiles > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many tiles");
+    }
+    if (tiles != n_tiles) return set_error(VCF_ERR_INVALID, "n_tiles %lld, the arrays have %lld", (long long)n_tiles, (long long)tiles);
+    return VCF_OK;
+}
+
+int64_t vcf_cbaac_tiled2d_planes_workspace(int64_t n_tiles, int64_t th, int64_t tw)
+{
+    if (n_tiles <= 0 || th < 1 || tw < 1) return 0;
+    // slots, per-tile bit counts, byte offsets (n_tiles + 1)
+    return n_tiles * slot_words_2d(th * tw) * 4 + n_tiles * 8 + (n_tiles + 1) * 8;
+}
+
+int64_t vcf_cbaac_tiled2d_planes_bound(int64_t n_tiles, int64_t th, int64_t tw)
+{
+    return n_tiles <= 0 || th < 1 || tw < 1 ? 0 : n_tiles * slot_words_2d(th * tw) * 4;
+}
+
+int vcf_cbaac_tiled2d_prior_planes(const uint8_t *buf_dev, int64_t buf_bytes, const vcf_plane_desc *desc_host,
+                                   const vcf_plane_desc *desc_dev, int64_t n_arrays, int64_t n_tiles, int64_t th,
+                                   int64_t tw, int32_t nclass, uint16_t *priors_dev, uint32_t *hist_dev, void *stream)
+{
+    if (int s = check_planes(desc_host, desc_dev, n_arrays, n_tiles, buf_bytes, th, tw, nclass, priors_dev)) return s;
+    if (!priors_dev || !hist_dev || !buf_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t rows = n_arrays * nclass * kCtx2d;
+    if (int s = hip_check(hipMemsetAsync(hist_dev, 0, 256 * sizeof(uint32_t) * rows, st), "hipMemsetAsync")) return s;
+    cbaac2d_hist_planes_kernel<<<(unsigned)n_tiles, 256, 0, st>>>(buf_dev, desc_dev, (int32_t)n_arrays, th, tw, nclass,
+                                                                  hist_dev);
+    if (int s = hip_check(hipGetLastError(), "cbaac2d_hist_planes_kernel")) return s;
+    cbaac_prior_classes_kernel<<<(unsigned)rows, 256, 0, st>>>(hist_dev, priors_dev);
+    return hip_check(hipGetLastError(), "cbaac_prior_classes_kernel");
+}
+
+int vcf_cbaac_tiled2d_encode_planes(const uint8_t *buf_dev, int64_t buf_bytes, const vcf_plane_desc *desc_host,
+                                    const vcf_plane_desc *desc_dev, int64_t n_arrays, int64_t n_tiles,
+                                    const uint16_t *priors_dev, int32_t nclass, int64_t th, int64_t tw,
+                                    uint8_t *out_dev, int64_t out_capacity, int64_t *tile_bytes_dev, void *ws_dev,
+                                    void *stream)
+{
+    if (int s = check_planes(desc_host, desc_dev, n_arrays, n_tiles, buf_bytes, th, tw, nclass, priors_dev)) return s;
+    if (out_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
+    if (!buf_dev || !ws_dev || !out_dev || !priors_dev || !tile_bytes_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t sw = slot_words_2d(th * tw);
+    uint32_t *slots = (uint32_t *)ws_dev;
+    int64_t *bits = (int64_t *)(slots + n_tiles * sw);
+    int64_t *offs = bits + n_tiles;
+    cbaac2d_encode_planes_kernel<<<(unsigned)n_tiles, 64, 0, st>>>(buf_dev, desc_dev, (int32_t)n_arrays, th, tw, slots, sw,
+                                                                   bits, priors_dev, nclass);
+    if (int s = hip_check(hipGetLastError(), "cbaac2d_encode_planes_kernel")) return s;
+    cbaac_tiled_scan_kernel<<<1, 1024, 0, st>>>(bits, n_tiles, offs, tile_bytes_dev);
+    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_scan_kernel")) return s;
+    cbaac_tiled_pack_kernel<<<(unsigned)n_tiles, 256, 0, st>>>(slots, sw, offs, out_dev, out_capacity);
+    return hip_check(hipGetLastError(), "cbaac_tiled_pack_kernel");
+}
+
+int vcf_cbaac_tiled2d_decode_planes(const uint8_t *in_dev, const int64_t *tile_offsets_dev,
+                                    const vcf_plane_desc *desc_host, const vcf_plane_desc *desc_dev, int64_t n_arrays,
+                                    int64_t n_tiles, const uint16_t *priors_dev, int32_t nclass, int64_t th, int64_t tw,
+                                    uint8_t *buf_dev, int64_t buf_bytes, void *stream)
+{
+    if (int s = check_planes(desc_host, desc_dev, n_arrays, n_tiles, buf_bytes, th, tw, nclass, priors_dev)) return s;
+    if (!in_dev || !tile_offsets_dev || !buf_dev || !priors_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    cbaac2d_decode_planes_kernel<<<(unsigned)n_tiles, 64, 0, (hipStream_t)stream>>>(
+        in_dev, tile_offsets_dev, desc_dev, (int32_t)n_arrays, th, tw, buf_dev, priors_dev, nclass);
+    return hip_check(hipGetLastError(), "cbaac2d_decode_planes_kernel");
 }
 
 }  // extern "C"

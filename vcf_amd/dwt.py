@@ -37,6 +37,22 @@ def subband_names(levels: int):
     return [f"LL_{levels}"] + [f"{s}_{r}" for r in range(levels, 0, -1) for s in ("LH", "HL", "HH")]
 
 
+def subband_planes(H: int, W: int, levels: int):
+    """[(name, byte offset in a frame's packed bytes, h, w, bytes per pixel)] in
+    file order: what unpack() slices, as numbers.  LL is 6 bytes per pixel (3
+    little-endian uint16), a detail subband 3."""
+    shapes, _, _ = layout(H, W, levels)
+    h, w = shapes[-1]
+    out = [(f"LL_{levels}", 0, h, w, 6)]
+    off = h * w * 6
+    for r in range(levels, 0, -1):
+        h, w = shapes[r - 1]
+        for s in ("LH", "HL", "HH"):
+            out.append((f"{s}_{r}", off, h, w, 3))
+            off += h * w * 3
+    return out
+
+
 def unpack(packed: np.ndarray, H: int, W: int, levels: int):
     """Packed bytes of one frame -> {name: u16 LL / u8 detail array (h x w x 3)}."""
     shapes, _, _ = layout(H, W, levels)

@@ -486,6 +486,141 @@ class FrameBatch2D(FrameBatch):
         return [fixed + rb[rst[f] + 4:rend[f]] + vb[vst[f]:vend[f]] for f in range(self.n_frames)]
 
 
+PLANE_DESC = np.dtype([("base", "<i8"), ("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("tile0", "<i4")])   # vcf_plane_desc
+
+
+def plane_descriptors(arrays, tile=TILE_2D):
+    """The descriptor table of a plane list (include/vcf_amd.h vcf_plane_desc)
+    for `arrays` = (byte offset in the buffer, H, W, C) per coded array, in
+    stream order -> (PLANE_DESC array, the list's tile count).  tile0 of array
+    a is the tile count of the arrays before it; host arithmetic only."""
+    th, tw = int(tile[0]), int(tile[1])
+    if th < 1 or tw < 1:
+        raise ValueError("tile sizes >= 1")
+    desc = np.zeros(len(arrays), PLANE_DESC)
+    tiles = 0
+    for a, (base, H, W, C) in enumerate(arrays):
+        if min(int(H), int(W), int(C)) < 1 or int(base) < 0:
+            raise ValueError(f"array {a}: {(base, H, W, C)}: a plane list holds non-empty arrays at offsets >= 0")
+        desc[a] = (int(base), int(H), int(W), int(C), tiles)
+        tiles += int(C) * (-(-int(H) // th)) * (-(-int(W) // tw))
+        if tiles > 0x7FFFFFFF:
+            raise ValueError("too many tiles")
+    return desc, tiles
+
+
+class PlaneBatch2D:
+    """Container version 4 over a plane list: arrays of different sizes
+    anywhere in one device buffer (a batch of 2D-DWT frames' packed subbands),
+    every tile of every array in one launch per stage
+    (vcf_cbaac_tiled2d_*_planes).  Array a's stream is, byte for byte,
+    TiledCBAACCodec(ctx2d=True).compress of that array alone.  launch()
+    enqueues, streams(shapes) waits and returns the containers; decode()
+    writes the arrays of parsed containers back to their places."""
+
+    def __init__(self, tile=TILE_2D, nclass: int = PRIOR_CLASSES, stream: Stream | None = None):
+        self.th, self.tw = int(tile[0]), int(tile[1])
+        self.nclass = int(nclass)
+        if self.th < 1 or self.tw < 1 or not 1 <= self.nclass <= 256:
+            raise ValueError("tile sizes >= 1, 1 .. 256 prior classes")
+        self.stream = stream if stream is not None else Stream()
+        self.scratch = _Scratch()
+        self.lock = threading.RLock()
+
+    def _describe(self, arrays, buf: DeviceBuffer):
+        desc, nt = plane_descriptors(arrays, (self.th, self.tw))
+        if not len(desc):
+            raise ValueError("empty plane list")
+        ends = desc["base"] + desc["H"].astype(np.int64) * desc["W"] * desc["C"]
+        if int(ends.max()) > buf.nbytes:
+            raise ValueError(f"plane list: an array ends at byte {int(ends.max())} of a {buf.nbytes}-byte buffer")
+        dd = self.scratch.get("desc", desc.nbytes)
+        dd.upload(desc, self.stream)
+        return desc, nt, dd
+
+    def launch(self, buf: DeviceBuffer, arrays, after: Stream | None = None) -> None:
+        """Enqueue the coding of `arrays` ((byte offset, H, W, C) each) of `buf`."""
+        from .device import Event
+        lib = L.lib()
+        if after is not None and after is not self.stream:
+            ev = Event()
+            ev.record(after)
+            self.stream.wait_event(ev)
+        self.desc, self.nt, dd = self._describe(arrays, buf)
+        na, K, h = len(self.desc), self.nclass, self.stream.handle
+        self.cap = int(lib.vcf_cbaac_tiled2d_planes_bound(self.nt, self.th, self.tw))
+        ws = self.scratch.get("ws", int(lib.vcf_cbaac_tiled2d_planes_workspace(self.nt, self.th, self.tw)))
+        self.out = self.scratch.get("out", self.cap)
+        self.sizes_dev = self.scratch.get("sizes", 8 * (self.nt + 1))
+        self.prior_dev = self.scratch.get("prior", 512 * NCTX_2D * K * na)
+        hist = self.scratch.get("hist", 1024 * NCTX_2D * K * na)
+        L.call("vcf_cbaac_tiled2d_prior_planes", buf.ptr, buf.nbytes, self.desc.ctypes.data, dd.ptr, na, self.nt, self.th,
+               self.tw, K, self.prior_dev.ptr, hist.ptr, h)
+        L.call("vcf_cbaac_tiled2d_encode_planes", buf.ptr, buf.nbytes, self.desc.ctypes.data, dd.ptr, na, self.nt,
+               self.prior_dev.ptr, K, self.th, self.tw, self.out.ptr, self.cap, self.sizes_dev.ptr, ws.ptr, h)
+
+    def streams(self, shapes) -> list:
+        """Wait for launch(); -> the version-4 container (bytes) of every
+        array, written with shapes[a] (H * W * C symbols: the shape the
+        single-array path would have been given)."""
+        na = len(self.desc)
+        sizes = np.empty(self.nt + 1, np.int64)
+        pri = np.empty((na, self.nclass * NCTX_2D, 256), np.uint16)
+        self.sizes_dev.download(sizes, self.stream)
+        self.prior_dev.download(pri, self.stream)
+        self.stream.synchronize()
+        payload = np.empty(int(sizes[-1]), np.uint8)
+        if payload.size:
+            self.out.download(payload, self.stream)
+            self.stream.synchronize()
+        offs = np.zeros(self.nt + 1, np.int64)
+        np.cumsum(sizes[:-1], out=offs[1:])
+        t0 = np.append(self.desc["tile0"].astype(np.int64), self.nt)
+        res = []
+        for a in range(na):
+            d = self.desc[a]
+            shape = tuple(int(s) for s in shapes[a])
+            if frame_dims(shape) != (int(d["H"]), int(d["W"]), int(d["C"])):
+                raise ValueError(f"array {a}: shape {shape} is not the coded {(d['H'], d['W'], d['C'])}")
+            res.append(pack2d(shape, self.th, self.tw, self.nclass, pri[a], sizes[t0[a]:t0[a + 1]],
+                              payload[offs[t0[a]]:offs[t0[a + 1]]].tobytes()))
+        return res
+
+    def decode(self, parsed, buf: DeviceBuffer, arrays) -> None:
+        """parsed[a] = _parse2d's fields of array a's container; its symbols
+        are written to arrays[a] = (byte offset, H, W, C) of `buf`, enqueued on
+        self.stream.  Every container is checked against its array, this
+        coder's tile and class count and its own payload before anything is
+        launched: ValueError otherwise."""
+        if len(parsed) != len(arrays):
+            raise ValueError("plane list: one container per array")
+        for a, (f, arr) in enumerate(zip(parsed, arrays)):
+            shape, th, tw, nclass, rows, tile_bytes, payload = f
+            if frame_dims(shape) != tuple(int(v) for v in arr[1:]):
+                raise ValueError(f"array {a}: a stream of shape {shape} where {tuple(arr[1:])} is expected")
+            if (th, tw, nclass) != (self.th, self.tw, self.nclass):
+                raise ValueError(f"array {a}: tile {th} x {tw}, {nclass} classes: not this coder's")
+            check_rows2d(rows, nclass)
+            if len(tile_bytes) != n_tiles2d(shape, th, tw) or int(np.sum(tile_bytes)) != len(payload):
+                raise ValueError(f"array {a}: tile sizes do not match the array or the payload")
+        desc, nt, dd = self._describe(arrays, buf)
+        tile_bytes = np.concatenate([np.asarray(f[5], np.int64) for f in parsed])
+        offs = np.zeros(nt + 1, np.int64)
+        np.cumsum(tile_bytes, out=offs[1:])
+        payload = np.frombuffer(b"".join(bytes(f[6]) for f in parsed), np.uint8)
+        pri = np.concatenate([check_rows2d(f[4], self.nclass) for f in parsed])
+        src = self.scratch.get("in", payload.size)
+        if payload.size:
+            src.upload(payload, self.stream)
+        ob = self.scratch.get("offs", offs.nbytes)
+        ob.upload(offs, self.stream)
+        pr = self.scratch.get("prior_in", pri.nbytes)
+        pr.upload(pri, self.stream)
+        L.call("vcf_cbaac_tiled2d_decode_planes", src.ptr, ob.ptr, desc.ctypes.data, dd.ptr, len(desc), nt, pr.ptr,
+               self.nclass, self.th, self.tw, buf.ptr, buf.nbytes, self.stream.handle)
+        self.stream.synchronize()   # desc, offs and the payload were uploaded from temporaries
+
+
 class Tiled2DCoder:
     """The version-4 GPU calls for one frame at a time, with a stream, a lock
     (as TiledCoder: the block codecs call the entropy codec from a thread
