@@ -2,7 +2,11 @@
 (interleaved ABBA rounds, §5.4 rule 24).  Variant 0 is the product library's
 kernel, the others the A/B library's (include/vcf_amd_ab.h).  DENSE=1: uniform
 random frames instead of S-smooth (every coefficient nonzero: the decode's
-worst case)."""
+worst case).  ROUNDS_JSON=path also writes every round's ms per launch of each
+variant and, for two variants A,B, the ABBA verdict: B counts as faster only if
+each round's B beats the A rounds next to it and the mean gain exceeds twice
+the spread (standard deviation) of the A rounds."""
+import json
 import os
 import sys
 
@@ -67,3 +71,16 @@ for v in variants:
     print(f"{'decode' if DECODE else 'encode'} variant {v}: median {t:.4f} ms/launch (min {min(res[v]):.4f}) -> "
           f"{alg / t / 1e6:.0f} GB/s ({alg / t / 1e6 / 8000:.1%} of 8 TB/s), "
           f"{F * H * W / t / 1e3:.0f} Mpix/s; per-round ratio to {variants[0]}: {ratio:.4f}", flush=True)
+if os.environ.get("ROUNDS_JSON"):
+    rec = {"what": "decode" if DECODE else "encode", "dense": os.environ.get("DENSE", "0") == "1", "variants": variants,
+           "ms_per_launch": {str(v): [round(x, 5) for x in res[v]] for v in variants}}
+    if len(variants) == 2:
+        a, b = (np.array(res[v]) for v in variants)
+        nb = [min(a[max(i - 1, 0):i + 2]) for i in range(ROUNDS)]   # the A rounds next to B's round i (and its own)
+        rec["verdict"] = {"every_B_below_neighbouring_A": bool(all(b[i] < nb[i] for i in range(ROUNDS))),
+                          "mean_A": round(float(a.mean()), 5), "mean_B": round(float(b.mean()), 5),
+                          "mean_gain_ms": round(float(a.mean() - b.mean()), 5), "std_A": round(float(a.std()), 5),
+                          "gain_over_2_std_A": bool(a.mean() - b.mean() > 2 * a.std())}
+    with open(os.environ["ROUNDS_JSON"], "w") as f:
+        json.dump(rec, f)
+    print(json.dumps(rec.get("verdict", {})), flush=True)

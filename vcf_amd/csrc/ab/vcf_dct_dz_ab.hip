@@ -243,7 +243,7 @@ __device__ __forceinline__ void load_block(const Geom &g, const uint8_t *src, in
     }
 }
 
-template <bool POW2, bool SUB, bool PERC, bool SDWA, bool PK = false, bool MEMONLY = false>
+template <bool POW2, bool SUB, bool PERC, bool SDWA, bool PK = false, bool MEMONLY = false, int SKIP = 0>
 __device__ __forceinline__ void encode_block(uint32_t (&raw)[8][6], const EncConsts &K, const FinalK &rowk,
                                              uint8_t *stage, int tid)
 {
@@ -270,11 +270,11 @@ __device__ __forceinline__ void encode_block(uint32_t (&raw)[8][6], const EncCon
             s2(n >> 3, n & 7, w >> 2);
         }
     } else if constexpr (PK && POW2 && !PERC) {
-        encode_block_channel_pk<0>(raw, rowk, K.qd[0], s0);
+        encode_block_channel_pk<0, SKIP>(raw, rowk, K.qd[0], s0);
         opaque(raw, (uint32_t)tid);
-        encode_block_channel_pk<1>(raw, rowk, K.qd[0], s1);
+        encode_block_channel_pk<1, SKIP>(raw, rowk, K.qd[0], s1);
         opaque(raw, (uint32_t)tid);
-        encode_block_channel_pk<2>(raw, rowk, K.qd[0], s2);
+        encode_block_channel_pk<2, SKIP>(raw, rowk, K.qd[0], s2);
     } else {
         encode_block_channel_fold<0, POW2, PERC, SDWA>(raw, rowk, K.qd, s0);
         opaque(raw, (uint32_t)tid);
@@ -291,8 +291,12 @@ __device__ __forceinline__ void encode_block(uint32_t (&raw)[8][6], const EncCon
 // entering or leaving its memory phase is not held behind the resident
 // workgroups' VALU streams (15, the default, measured 1-2.5 % faster than 0
 // over three boxes, ABBA; variants 12-15 and 16 = PRIO 0 are the A/B records).
+// SKIP: 0 every row pair of the packed path is transformed (the product's
+// kernel before the zero test, variant 20); 1 row pairs 1..3 that a wave proves
+// zero are skipped and their zero bytes written one by one (variant 21; the
+// product zeroes rows 2..7 of the image beforehand instead).
 template <bool POW2, bool SUB, bool PERC, bool PAD, bool SDWA = true, bool PK = false, bool MEMONLY = false,
-          int STREAMS = 0, int NT = 0, bool XCD = true, int LD = 1, int PRIO = 15, bool FA = true>
+          int STREAMS = 0, int NT = 0, bool XCD = true, int LD = 1, int PRIO = 15, bool FA = true, int SKIP = 0>
 __global__ __launch_bounds__(kTile) void dct_dz_encode_kernel(const uint8_t *__restrict__ rgb,
                                                               uint8_t *__restrict__ kout, Geom g,
                                                               EncConsts K, FinalK rowk)
@@ -320,7 +324,7 @@ __global__ __launch_bounds__(kTile) void dct_dz_encode_kernel(const uint8_t *__r
         if (PRIO & 3) __builtin_amdgcn_s_setprio(PRIO & 3);
         load_block<PAD, LD, FA>(g, rgb + frame * g.in_stride, by, bx, raw);
         if (PRIO & 3) __builtin_amdgcn_s_setprio(0);
-        encode_block<POW2, SUB, PERC, SDWA, PK, MEMONLY>(raw, K, rowk, stage, tid);
+        encode_block<POW2, SUB, PERC, SDWA, PK, MEMONLY, SKIP>(raw, K, rowk, stage, tid);
     }
     __syncthreads();
     if (PRIO >> 2) __builtin_amdgcn_s_setprio(PRIO >> 2);
@@ -1013,7 +1017,7 @@ int vcf_dct_dz_encode_variant(int variant, const uint8_t *rgb_dev, int64_t n_fra
         return dct_any_encode_u8(rgb_dev, n_frames, H, W, block_size, Q, flags, k_dev, stream);
     int rc = check_args(rgb_dev, k_dev, n_frames, H, W, block_size, Q, flags, false);
     if (rc != VCF_OK) return rc;
-    if (variant < 0 || variant > 19) return set_error(VCF_ERR_INVALID, "unknown encode variant %d", variant);
+    if (variant < 0 || variant > 21) return set_error(VCF_ERR_INVALID, "unknown encode variant %d", variant);
     if (n_frames == 0) return VCF_OK;
     Geom g;
     make_geom(H, W, g);
@@ -1089,6 +1093,24 @@ int vcf_dct_dz_encode_variant(int variant, const uint8_t *rgb_dev, int64_t n_fra
         hipLaunchKernelGGL((dct_dz_encode_kernel<true, true, false, false, true, true, false, 0, 0, true, 1, 15, false>),
                            grid, dim3(kTile), 0, (hipStream_t)stream, rgb_dev, k_dev, g, K, rowk);
         return hip_check(hipGetLastError(), "variant 17 launch");
+    }
+    if (variant == 20 || variant == 21) {   // A/B: the packed kernel without the zero test (20), with it (21)
+        if (!(pow2 && !perc)) return set_error(VCF_ERR_INVALID, "variants 20/21: pow2 Q, no -p");
+        for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
+            const dim3 grid(g.tiles_per_frame, (unsigned)std::min<int64_t>(65535, n_frames - f0));
+#define VCF_ENC_SKIP(SB, PD, SK)                                                                                   \
+    if (sub == SB && pad == PD && (variant == 21) == (SK == 1))                                                     \
+        hipLaunchKernelGGL((dct_dz_encode_kernel<true, SB, false, PD, true, true, false, 0, 0, true, 1, 15, true, SK>), \
+                           grid, dim3(kTile), 0, (hipStream_t)stream, rgb_dev + f0 * g.in_stride,                   \
+                           k_dev + f0 * g.out_stride, g, K, rowk);
+            VCF_ENC_SKIP(true, false, 0) else VCF_ENC_SKIP(true, true, 0) else VCF_ENC_SKIP(false, false, 0)
+            else VCF_ENC_SKIP(false, true, 0) else VCF_ENC_SKIP(true, false, 1) else VCF_ENC_SKIP(true, true, 1)
+            else VCF_ENC_SKIP(false, false, 1) else VCF_ENC_SKIP(false, true, 1)
+#undef VCF_ENC_SKIP
+            rc = hip_check(hipGetLastError(), "variant 20/21 launch");
+            if (rc != VCF_OK) return rc;
+        }
+        return VCF_OK;
     }
     if (variant == 11) {   // A/B: variant 5 with the earlier non-temporal input loads
         if (!(pow2 && !perc && sub && !pad)) return set_error(VCF_ERR_INVALID, "variant 11: pow2 Q, aligned, default flags");

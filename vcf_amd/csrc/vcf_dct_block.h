@@ -667,6 +667,84 @@ VCF_HD void encode_block_channel_fold(const uint32_t (&raw)[8][6], const FinalK 
     }
 }
 
+// ---- provably zero rows of the row pass (power-of-two Q, no -p) -----------
+// After the column pass, row i of v holds u = v[i][0..7] in the kernel's units
+// (the column pass carries 2^-(chs + inv(i))), and the row pass dct2_8f(u,
+// row_final_k(Q)) yields q[j] = x / (Q 2^e) itself, whose index is trunc(q[j]):
+// 0 iff |q[j]| < 1 (and -0.0 converts to 0 too).  With the fp32 constants
+// taken as exact reals, that row pass is the linear map q = R u with
+// R = (orthonormal 8-point DCT-II) / Q to 1e-7: its largest entry is
+// 0.4903927 / Q < 0.5 / Q, so in exact arithmetic
+//     |q[j]| <= (0.5 / Q) * S,   S = sum_x |u[x]|          (L1 form).
+// Slack, both parts explicit:
+//   * the fp32 rounding of pocketfft's operation sequence: every output is a
+//     sum over signal paths of at most 8 rounded operations, so the computed
+//     q[j] is off by at most g8 * (A |u|)[j], g8 = 8 * 2^-24 / (1 - 8 * 2^-24),
+//     where A is the same flow graph with every constant and sign made
+//     positive (cancelling paths counted in full): its largest entry is
+//     0.9807853 / Q < 1 / Q.  So |computed q[j]| < (0.4903927 + 4.8e-7) S / Q;
+//   * the bound's own arithmetic: S is summed in fp32 from non-negative terms
+//     (7 additions, relative error below 7 * 2^-24 in any order), and the
+//     product with the scale rounds once more (2^-24): together below 4.8e-7.
+// The test is  fl(fl(S) * kb) < 1  with kb = 0.5 * (1 + 2^-10) / Q, which
+// exceeds (0.4903927 + 4.8e-7) / (1 - 4.8e-7) / Q by 2 %: a row that passes
+// has every |computed q[j]| < 1 - 0.019.  kb is exact: qd[0] = 2^-3 / Q is a
+// power of two and 4 + 2^-8 has 11 significant bits.  No value underflows: a
+// nonzero u is a sum of products of integers below 2^11 with fp32 constants,
+// far above the subnormal range for every Q the packed path takes (<= 2^30).
+// A NaN cannot occur and would fail the test (the comparison is false).
+// tests/test_block_math_skip.py checks the claim against the real dct2_8f and
+// cvt_trunc_i32 at the boundary, and that the bound is tight enough for the
+// benchmark's frames (rows 2..7 of every 64-block group pass at Q = 32).
+constexpr float kRowSkipC = 4.0f + 0.00390625f;   // (0.5 * (1 + 2^-10)) / 2^-3
+
+VCF_HD float row_skip_scale(float qd0)   // qd0 = 2^-3 / Q  ->  kb
+{
+    return qd0 * kRowSkipC;
+}
+
+VCF_HD float abs_f(float x)
+{
+#if defined(__HIPCC__)
+    return __builtin_fabsf(x);   // a source modifier, no instruction
+#else
+    return fabsf(x);
+#endif
+}
+
+// |a| + |b| as one v_add_f32 with |.| source modifiers.  The empty asm keeps
+// the SLP vectorizer from pairing the two rows' sums into v_pk_add_f32, which
+// has no |.| modifier (one v_and per operand instead: twice the instructions).
+VCF_HD float abs_add(float a, float b)
+{
+    float s = abs_f(a) + abs_f(b);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(s));
+#endif
+    return s;
+}
+
+VCF_HD float row_abs_sum(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7)
+{
+    return abs_add(abs_add(abs_add(a0, a1), abs_add(a2, a3)), abs_add(abs_add(a4, a5), abs_add(a6, a7)));
+}
+
+// true: every index of the two rows whose |.| sums are sa and sb is 0
+VCF_HD bool row_pair_is_zero(float sa, float sb, float kb)
+{
+    return __builtin_fmaxf(sa, sb) * kb < 1.0f;
+}
+
+// every active lane of the wave agrees (host build: the one "lane")
+VCF_HD bool wave_all(bool pred)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(!pred) == 0;
+#else
+    return pred;
+#endif
+}
+
 #if defined(__HIPCC__)
 // ---- packed-fp32 channel encoder (POW2 Q, no -p) --------------------------
 // The same arithmetic as encode_block_channel_fold<C, true, false, true>, two
@@ -713,7 +791,14 @@ VCF_HD void fold_columns_pk(const uint32_t (&raw)[8][6], uint32_t magic, const F
     }
 }
 
-template <int C, typename Sink>
+// SKIP: 0 every row pair is transformed; 1, 2: row pairs 1..3 (rows 2..7) are
+// tested first (row_pair_is_zero above; dep0 = qd[0] = 2^-3 / Q) and a pair
+// that every block of the wave proves zero is branched around -- its
+// transposes, transform, 16 conversions and 16 sinks.  The branch is
+// wave-uniform.  1: the sink still gets the skipped pair's 16 zero indices;
+// 2: it gets nothing (the caller has zeroed rows 2..7 of its image).  Row
+// pair 0 carries DC and is always computed.
+template <int C, int SKIP = 0, typename Sink>
 VCF_HD void encode_block_channel_pk(const uint32_t (&raw)[8][6], const FinalK &rowk, float dep0, Sink &&sink)
 {
     constexpr float cs = C == 1 ? 0.5f : 0.25f;
@@ -723,8 +808,24 @@ VCF_HD void encode_block_channel_pk(const uint32_t (&raw)[8][6], const FinalK &r
     uint32_t magic = ycocg_magic_word<C>();
     VCF_OPAQUE(magic);
     fold_columns_pk<C, 0>(raw, magic, colk, v, dep);
+    const float kb = row_skip_scale(dep0);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
+        if (SKIP && p > 0) {
+            const vcf_f2(&a)[4] = v[2 * p], (&b)[4] = v[2 * p + 1];
+            const float sa = row_abs_sum(a[0].x, a[0].y, a[1].x, a[1].y, a[2].x, a[2].y, a[3].x, a[3].y);
+            const float sb = row_abs_sum(b[0].x, b[0].y, b[1].x, b[1].y, b[2].x, b[2].y, b[3].x, b[3].y);
+            if (wave_all(row_pair_is_zero(sa, sb, kb))) {
+                if (SKIP == 1) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        sink(2 * p, j, 0u);
+                        sink(2 * p + 1, j, 0u);
+                    }
+                }
+                continue;
+            }
+        }
         vcf_f2 r[8];
 #pragma unroll
         for (int xp = 0; xp < 4; ++xp) {

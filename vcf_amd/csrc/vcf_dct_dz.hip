@@ -21,8 +21,11 @@
 //     straight from registers.
 // The A/B variants measured against these live in the
 // experimental library (csrc/ab/, libvcf_amd_ab.so), not here.
-// The encode is VALU-issue bound (profiles/).  No MFMA: the
-// transforms must follow pocketfft's rounding sequence exactly.
+// The encode sits between its arithmetic and its memory traffic (DESIGN.md §5:
+// compute-only and memory-only take about the same time and overlap
+// imperfectly at 3 waves per SIMD), so the packed path drops the row
+// transforms whose indices it can prove zero beforehand.  No
+// MFMA: the transforms must follow pocketfft's rounding sequence exactly.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -251,11 +254,13 @@ __device__ __forceinline__ void encode_block(uint32_t (&raw)[8][6], const EncCon
         else stage[i * (T * 24) + tid * 24 + j * 3 + 2] = (uint8_t)w;
     };
     if constexpr (PK && POW2 && !PERC) {
-        encode_block_channel_pk<0>(raw, rowk, K.qd[0], s0);
+        // rows 2..7 of the image are zero already (zero_wave_rows): a row pair
+        // that the wave proves zero writes nothing
+        encode_block_channel_pk<0, 2>(raw, rowk, K.qd[0], s0);
         opaque(raw, (uint32_t)tid);
-        encode_block_channel_pk<1>(raw, rowk, K.qd[0], s1);
+        encode_block_channel_pk<1, 2>(raw, rowk, K.qd[0], s1);
         opaque(raw, (uint32_t)tid);
-        encode_block_channel_pk<2>(raw, rowk, K.qd[0], s2);
+        encode_block_channel_pk<2, 2>(raw, rowk, K.qd[0], s2);
     } else {
         encode_block_channel_fold<0, POW2, PERC, true>(raw, rowk, K.qd, s0);
         opaque(raw, (uint32_t)tid);
@@ -265,7 +270,43 @@ __device__ __forceinline__ void encode_block(uint32_t (&raw)[8][6], const EncCon
     }
 }
 
-// PK: packed-fp32 transforms (power-of-two Q, no -p).  Wave priority
+// A wave's own part of rows 2..7 of the LDS image, zeroed with 16-byte
+// writes.  The 64 blocks of wave w own bytes [192 w, 192 w + 192) of each of
+// the 48 subband runs (i, j), i >= 2 -- 12 chunks per run, written by lanes
+// (run & 3, chunk) = (lane >> 4, lane & 15 < 12), 12 runs each -- or, for -x,
+// bytes [1536 w, 1536 w + 1536) of each of the 6 pixel rows i >= 2: 96 chunks
+// per row, lanes 0..63 and again lanes 0..31.  Every offset after the lane's
+// base is a compile-time constant.  Only the wave itself writes these bytes
+// afterwards (its blocks' index bytes), and a wave's LDS operations execute in
+// order, so a wave-level fence for the compiler is all that orders the two --
+// no workgroup barrier.
+template <bool SUB, int T>
+__device__ __forceinline__ void zero_wave_rows(uint8_t *stage, int tid)
+{
+    const int w = tid >> 6, l = tid & 63;
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    if (SUB) {
+        if ((l & 15) < 12) {
+            uint8_t *p = stage + (16 + (l >> 4)) * (T * 3) + w * 192 + (l & 15) * 16;
+#pragma unroll
+            for (int r = 0; r < 12; ++r) *reinterpret_cast<u32x4 *>(p + r * 4 * (T * 3)) = z;
+        }
+    } else {
+        uint8_t *p = stage + 2 * (T * 24) + w * 1536 + l * 16;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            *reinterpret_cast<u32x4 *>(p + i * (T * 24)) = z;
+            if (l < 32) *reinterpret_cast<u32x4 *>(p + i * (T * 24) + 1024) = z;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// PK: packed-fp32 transforms (power-of-two Q, no -p), with row pairs 1..3 of a
+// channel skipped where the whole wave proves their indices zero
+// (vcf_dct_block.h: row_pair_is_zero); rows 2..7 of the image are zeroed while
+// the input loads are in flight, so a skipped pair writes nothing.  Wave priority
 // (s_setprio) 3 while the input loads issue and during the copy-out, 0 during
 // the transforms: a workgroup entering or leaving its memory phase is not held
 // behind the resident workgroups' VALU streams (1-2.5 % faster than none over
@@ -288,16 +329,19 @@ __global__ __launch_bounds__(T) void dct_dz_encode_kernel(const uint8_t *__restr
     const int tile = (int)(t - (unsigned)frame * gridDim.x);
     const int n0 = tile * T;
     const int nvalid = min(T, g.nblocks - n0);
+    uint32_t raw[8][6];
     if (tid < nvalid) {
         int by, bx;
         tile_block(g, n0 + tid, by, bx);
         rowbase[tid] = block_rowbase<SUB>(g, by, bx);
-        uint32_t raw[8][6];
         __builtin_amdgcn_s_setprio(3);
         load_block<PAD>(g, rgb + frame * g.in_stride, by, bx, raw);
         __builtin_amdgcn_s_setprio(0);
-        encode_block<POW2, SUB, PERC, PK, T>(raw, K, rowk, stage, tid);
     }
+    // every lane of the wave, also those past a partial tile's end: the chunks
+    // a lane zeroes are not its own block's
+    if constexpr (PK && POW2 && !PERC) zero_wave_rows<SUB, T>(stage, tid);
+    if (tid < nvalid) encode_block<POW2, SUB, PERC, PK, T>(raw, K, rowk, stage, tid);
     __syncthreads();
     __builtin_amdgcn_s_setprio(3);
     if (nvalid == T && g.vec) move_runs_full<SUB, T>(g, stage, rowbase, kout + frame * g.out_stride);
