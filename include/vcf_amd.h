@@ -205,6 +205,17 @@ int vcf_klt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t
  * arguments are checked before any device work; work is enqueued on the
  * caller's stream.  The padded shape is vcf_klt_padded_shape's. */
 
+/* The launch plan for this shape and block size, computed by the code the
+ * launches call: TB, the blocks of a frame and channel that one workgroup of
+ * vcf_lbt_dz_encode (decode = 0) or vcf_lbt_dz_decode (decode != 0) owns; the
+ * LDS class of that kernel (0, 1, 2: 48, 80, 156 KiB per workgroup); the
+ * workgroups (tiles) per frame; and for vcf_lbt_moments the workgroups per
+ * frame and channel (chunks of 2048 blocks) and the blocks one of them stages
+ * in LDS at a time.  Host only; the shape and block size rules of
+ * vcf_lbt_dz_encode. */
+int vcf_lbt_tile_plan(int32_t H, int32_t W, int32_t block_size, int32_t decode, int32_t *TB, int32_t *lds_class,
+                      int32_t *tiles, int32_t *moment_chunks, int32_t *moment_stage_blocks);
+
 /* Per frame, pooled over the three channels: s1_dev (n_frames x D float64) =
  * sum of x, s2_dev (n_frames x D x D float64, full symmetric) = sum of x x^T
  * over the 3 N blocks, x = the YCoCg values after the zero pad and -128.

@@ -13,6 +13,7 @@ import pytest
 from conftest import GOLDEN
 
 import lbt_restated as R
+import lbt_sweep_cases as S
 
 
 def lbt_manifest():
@@ -254,3 +255,163 @@ def test_argument_errors_before_any_device_work():
         assert fn(d, 1, 16, 16, 8, 32, 0, d, None, d, None) == L.VCF_ERR_INVALID
         assert fn(d, 1, 0, 16, 8, 32, 0, d, d, d, None) == L.VCF_ERR_INVALID
     assert lib.vcf_last_error()
+
+
+# ---- the block-size sweep (tests/lbt_sweep_cases.py): what keeps it honest --------
+def _shares(name):
+    """The conditions every sweep case meets, measured on the restatement alone."""
+    c = S.by_name(name)
+    D = c["B"] ** 2
+    d = S.decoded(name)
+    pb = float(R.pixel_boundary(d["pre"], d["mag"], D).mean())
+    saturated = float(np.mean((d["rgb"] == 0) | (d["rgb"] == 255)))
+    return c, D, pb, saturated
+
+
+@pytest.mark.parametrize("name", S.ENCODE_IDS)
+def test_sweep_encode_cases_show_their_arithmetic(name):
+    """Few positions on the boundary sets (the GPU tests' cap), at most half of the decoded pixels
+    clipped; at Q = 1 the clamp to 0..255 is exercised and does not dominate, at Q = 32 the indices
+    are not all 128."""
+    c, D, pb, saturated = _shares(name)
+    e = S.encoded(name)
+    ib = float(R.index_boundary(e["pre"], e["mag"], D).mean())
+    clipped = float(np.mean((e["k"] == 0) | (e["k"] == 255)))
+    nonzero = float(np.mean(e["k"] != 128))
+    print(f"{name}: index boundary {ib:.5f}, pixel boundary {pb:.5f}, saturated {saturated:.4f}, clipped indices "
+          f"{clipped:.4f}, indices != 128 {nonzero:.4f}")
+    assert e["k"].shape == R.padded_shape(*S.FRAME, c["B"])[:2] + (3,)
+    assert ib <= 0.01 and pb <= 0.01 and saturated <= 0.5
+    if c["Q"] == 1:
+        assert 0.005 <= clipped <= 0.5
+    if c["Q"] == 32:
+        assert nonzero >= 0.2
+
+
+@pytest.mark.parametrize("name", S.RAW_IDS)
+def test_sweep_raw_cases_are_fit_to_decode(name):
+    """Index frames no encoder writes: few pixels on the boundary set, at most half clipped, and at
+    Q = 300 the int16 dequantizer does wrap."""
+    c, D, pb, saturated = _shares(name)
+    k = S.raw_k(name)
+    wrapping = np.count_nonzero(np.abs(c["Q"] * (k.astype(np.int64) - 128)) > 32767)
+    print(f"{name}: pixel boundary {pb:.5f}, saturated {saturated:.4f}, {wrapping} wrapping indices")
+    assert pb <= 0.01 and saturated <= 0.5
+    if c["Q"] == 300:
+        assert wrapping >= 10
+    else:
+        assert c["Q"] == 1 and len(np.unique(k)) == 256
+
+
+def test_sweep_cases_are_the_ones_the_issue_names():
+    assert len(S.ENCODE) == 7 * 2 * 3 + 4 and len(set(S.ENCODE_IDS)) == len(S.ENCODE)
+    assert {(c["B"], c["flags"], c["Q"]) for c in S.ENCODE[:42]} == \
+        {(B, f, Q) for B in range(2, 9) for f in (0, R.NO_SUBBANDS) for Q in (1, 8, 32)}
+    assert {(c["B"], c["flags"], c["Q"]) for c in S.ENCODE[42:]} == {(B, f, 8) for B in (5, 8) for f in (2, 3)}
+    for Q, seed0 in ((1, 30), (300, 40)):
+        raw = [c for c in S.RAW if c["Q"] == Q and not c["flags"] & R.PERCEPTUAL]
+        assert [(c["B"], c["seed"]) for c in raw] == [(B, seed0 + B) for B in range(2, 9)]
+        assert [c["flags"] for c in raw] in ([0, 1] * 3 + [0], [1, 0] * 3 + [1])
+    assert [(c["B"], c["Q"]) for c in S.RAW if c["flags"] & R.PERCEPTUAL] == [(8, 300)]
+    for B in S.SWEEP_B:
+        w = S.we(B).astype(np.float64)
+        assert S.we(B).dtype == np.float32 and np.allclose(w @ w.T, np.eye(B * B), atol=1e-6)
+        assert np.array_equal(S.wd(B), S.we(B).T)
+
+
+def _tile_plan(H, W, B, decode):
+    import vcf_amd.lbt as G
+    return G.tile_plan(H, W, B, decode)
+
+
+def _blocks(H, W, B):
+    Hp, Wp = R.padded_shape(H, W, B)[:2]
+    return (Hp // B) * (Wp // B)
+
+
+def _staged(N, chunks, tbm, chunk=2048):
+    """Staged tiles of the moments kernel per frame and channel, and the size of the last one."""
+    assert chunks == -(-N // chunk)
+    sizes = [min(tbm, n - t0) for n in (min(chunk, N - c * chunk) for c in range(chunks)) for t0 in range(0, n, tbm)]
+    return len(sizes), sizes[-1]
+
+
+def test_sweep_reaches_every_launch_class():
+    """What the sweep launches, from vcf_lbt_tile_plan (the code the launches call): at every B at
+    least 3 encode and 3 decode workgroups per frame with a partial last tile that is no whole
+    number of waves, above one wave for some B and below it for another; every LDS class that any
+    B = 2 .. 8 can reach, for encode and for decode; at least 2 staged moment tiles at every B, and
+    2 moment chunks at two values of B or more.  Retuning make_geom so that the sweep stops reaching
+    one of these fails here."""
+    H, W = S.FRAME
+    table = {2: (7875, 8, 707), 3: (3500, 4, 812), 4: (2014, 4, 478), 5: (1260, 4, 300), 6: (875, 5, 107),
+             7: (660, 6, 20), 8: (513, 5, 1)}
+    met = {False: set(), True: set()}
+    lasts, chunked, restaged = [], [], []
+    print(f"{'B':>2} {'blocks':>6} {'TB':>5} {'enc class':>9} {'dec class':>9} {'tiles':>5} {'last':>5} {'chunks':>6} "
+          f"{'staged':>6} {'of':>5} {'last staged':>11}")
+    for B in S.SWEEP_B:
+        N = _blocks(H, W, B)
+        enc, dec = _tile_plan(H, W, B, False), _tile_plan(H, W, B, True)
+        assert enc[0] == dec[0] and enc[2:] == dec[2:]
+        TB, _, tiles, chunks, tbm = enc
+        last = N - (tiles - 1) * TB
+        n_staged, last_staged = _staged(N, chunks, tbm)
+        print(f"{B:>2} {N:>6} {TB:>5} {enc[1]:>9} {dec[1]:>9} {tiles:>5} {last:>5} {chunks:>6} {n_staged:>6} {tbm:>5} "
+              f"{last_staged:>11}")
+        assert tiles == -(-N // TB) and tiles >= 3
+        assert 0 < last < TB and last % 64 != 0
+        assert (N, tiles, last) == table[B]
+        assert n_staged >= 2
+        met[False].add(enc[1])
+        met[True].add(dec[1])
+        lasts.append(last)
+        chunked.append(chunks >= 2)
+        restaged.append(min(N, 2048) > tbm)      # one workgroup stages more than once
+    assert any(x > 64 for x in lasts) and any(x < 64 for x in lasts)
+    assert sum(chunked) >= 2 and sum(restaged) >= 2
+    sizes = (1, 9, 37, 150, 480, 1080, 2160)
+    for decode in (False, True):
+        reachable = {_tile_plan(h, w, B, decode)[1] for B in range(2, 9) for h in sizes for w in sizes}
+        print(f"{'decode' if decode else 'encode'}: LDS classes met {sorted(met[decode])}, reachable {sorted(reachable)}")
+        assert met[decode] == reachable
+    # the second frame of the moments test: two chunks, 68 blocks in the second
+    N = _blocks(*S.CHUNK_FRAME, 8)
+    chunks, tbm = _tile_plan(*S.CHUNK_FRAME, 8, False)[3:]
+    assert (N, chunks, N - 2048) == (2116, 2, 68) and _staged(N, chunks, tbm)[1] == 68
+
+
+def test_tile_plan_errors():
+    import ctypes
+
+    import vcf_amd._lib as L
+    v = [ctypes.c_int32(-7) for _ in range(5)]
+    p = [ctypes.byref(x) for x in v]
+    f = L.lib().vcf_lbt_tile_plan
+    for B, decode in ((1, 0), (9, 1)):
+        assert f(150, 210, B, decode, *p) == L.VCF_ERR_UNSUPPORTED
+    assert f(0, 210, 8, 0, *p) == L.VCF_ERR_INVALID
+    assert f(150, -1, 8, 1, *p) == L.VCF_ERR_INVALID
+    assert f(150, 210, 8, 0, None, None, None, None, None) == L.VCF_ERR_INVALID
+    for i in range(5):
+        assert f(150, 210, 8, 0, *[None if j == i else p[j] for j in range(5)]) == L.VCF_ERR_INVALID
+    assert all(x.value == -7 for x in v)          # a refused call writes nothing
+    assert f(150, 210, 8, 0, *p) == 0 and all(x.value >= 0 for x in v)
+    with pytest.raises(NotImplementedError):
+        _tile_plan(150, 210, 9, False)
+
+
+def test_proxy_scale_comes_from_the_fixtures():
+    """c = the largest d_ref / d_proxy over the 20-epoch fixtures: torch's float32 run lies d_ref from
+    the float64 restatement, the restatement's own float32 run d_proxy.  The GPU test of the block
+    sizes without a fixture bounds its distance by 4 x c x d_proxy."""
+    ratios = S.proxy_ratios()
+    for name, r in ratios.items():
+        print(f"{name}: d_ref / d_proxy {r:.3f}")
+    assert set(ratios) == {c["name"] for c in SHORT} and len(ratios) == 7
+    assert all(np.isfinite(r) and r > 0 for r in ratios.values())
+    assert S.proxy_scale() == max(ratios.values())
+    for B in S.TRAIN_B:
+        t = S.trained(B)
+        print(f"B = {B}: d_proxy {t['d_proxy']:.3e}, bound {4 * S.proxy_scale() * t['d_proxy']:.3e}")
+        assert t["d_proxy"] > 0

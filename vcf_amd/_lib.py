@@ -102,6 +102,7 @@ SIGNATURES = {
     "vcf_klt_moments": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],
     "vcf_klt_dz_encode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P, _P],
     "vcf_klt_dz_decode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P, _P],
+    "vcf_lbt_tile_plan": [_I32, _I32, _I32, _I32, _PI32, _PI32, _PI32, _PI32, _PI32],
     "vcf_lbt_moments": [_P, _I64, _I32, _I32, _I32, _P, _P, _P],
     "vcf_lbt_train": [_P, _P, _I64, _I32, _I64, _I32, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P],
     "vcf_lbt_dz_encode": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _P, _P, _P],

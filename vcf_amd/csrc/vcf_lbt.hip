@@ -555,6 +555,28 @@ int lds_class(long long bytes)
     return -1;
 }
 
+// What the launches use, and what vcf_lbt_tile_plan reports: the encode (or decode) grid and LDS
+// class, and the moments kernel's chunks per frame and blocks per staged tile.
+struct LbtPlan {
+    int cls;       // index into kLds, -1: the tile does not fit
+    int tiles;     // encode / decode workgroups per frame
+    int nt, T;     // moments: 8-wide coefficient groups, and their upper-triangle pairs
+    int chunks;    // moments: workgroups per frame and channel
+    int tbm;       // moments: blocks staged in LDS at a time
+};
+
+LbtPlan make_plan(const LbtGeom &g, bool decode)
+{
+    LbtPlan p;
+    p.cls = lds_class(decode ? dec_lds(g) : enc_lds(g));
+    p.tiles = (g.N + g.TB - 1) / g.TB;
+    p.nt = (g.D + 7) / 8;
+    p.T = p.nt * (p.nt + 1) / 2;
+    p.chunks = (g.N + kMomChunk - 1) / kMomChunk;
+    p.tbm = std::min(kMomChunk, kMomLds / (p.nt * 8));
+    return p;
+}
+
 int check_shape(int32_t H, int32_t W, int32_t B)
 {
     if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad shape %d x %d", H, W);
@@ -600,6 +622,25 @@ using namespace vcf;
 
 extern "C" {
 
+int vcf_lbt_tile_plan(int32_t H, int32_t W, int32_t block_size, int32_t decode, int32_t *TB, int32_t *lds_class,
+                      int32_t *tiles, int32_t *moment_chunks, int32_t *moment_stage_blocks)
+{
+    if (!TB || !lds_class || !tiles || !moment_chunks || !moment_stage_blocks)
+        return set_error(VCF_ERR_INVALID, "null pointer");
+    const int rc = check_shape(H, W, block_size);
+    if (rc != VCF_OK) return rc;
+    LbtGeom g;
+    make_geom(H, W, block_size, g);
+    const LbtPlan p = make_plan(g, decode != 0);
+    if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
+    *TB = g.TB;
+    *lds_class = p.cls;
+    *tiles = p.tiles;
+    *moment_chunks = p.chunks;
+    *moment_stage_blocks = p.tbm;
+    return VCF_OK;
+}
+
 int vcf_lbt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                     double *s1_dev, double *s2_dev, void *stream)
 {
@@ -611,13 +652,11 @@ int vcf_lbt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t
     if (rc != VCF_OK) return rc;
     rc = hip_check(hipMemsetAsync(s2_dev, 0, (size_t)(n_frames * D * D * 8), (hipStream_t)stream), "hipMemsetAsync(S2)");
     if (rc != VCF_OK) return rc;
-    const int nt = (g.D + 7) / 8, T = nt * (nt + 1) / 2;
-    const int tbm = std::min(kMomChunk, kMomLds / (nt * 8));
-    const unsigned chunks = (unsigned)((g.N + kMomChunk - 1) / kMomChunk);
+    const LbtPlan p = make_plan(g, false);
     for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid(chunks, 3, (unsigned)std::min<int64_t>(65535, n_frames - f0));
+        const dim3 grid((unsigned)p.chunks, 3, (unsigned)std::min<int64_t>(65535, n_frames - f0));
         hipLaunchKernelGGL(lbt_moments_kernel, grid, dim3(kMomThreads), 0, (hipStream_t)stream,
-                           rgb_dev + f0 * g.rgb_stride, s1_dev + f0 * D, s2_dev + f0 * D * D, g, nt, T, tbm);
+                           rgb_dev + f0 * g.rgb_stride, s1_dev + f0 * D, s2_dev + f0 * D * D, g, p.nt, p.T, p.tbm);
         rc = hip_check(hipGetLastError(), "lbt_moments_kernel launch");
         if (rc != VCF_OK) return rc;
     }
@@ -658,12 +697,13 @@ int vcf_lbt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
     LbtScale pq;
     rc = make_scale(block_size, flags, pq);
     if (rc != VCF_OK) return rc;
-    const int cls = lds_class(enc_lds(g));
+    const LbtPlan p = make_plan(g, false);
+    const int cls = p.cls;
     if (cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;
     const long long DD = (long long)g.D * g.D;
     for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)((g.N + g.TB - 1) / g.TB), (unsigned)std::min<int64_t>(65535, n_frames - f0));
+        const dim3 grid((unsigned)p.tiles, (unsigned)std::min<int64_t>(65535, n_frames - f0));
         const uint8_t *in = rgb_dev + f0 * g.rgb_stride;
         const float *w = we_dev + f0 * DD;
         const float *m = mean_dev + f0;
@@ -691,12 +731,13 @@ int vcf_lbt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t
     LbtScale pq;
     rc = make_scale(block_size, flags, pq);
     if (rc != VCF_OK) return rc;
-    const int cls = lds_class(dec_lds(g));
+    const LbtPlan p = make_plan(g, true);
+    const int cls = p.cls;
     if (cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;
     const long long DD = (long long)g.D * g.D;
     for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)((g.N + g.TB - 1) / g.TB), (unsigned)std::min<int64_t>(65535, n_frames - f0));
+        const dim3 grid((unsigned)p.tiles, (unsigned)std::min<int64_t>(65535, n_frames - f0));
         const uint8_t *in = k_dev + f0 * g.k_stride;
         const float *w = wd_dev + f0 * DD;
         const float *m = mean_dev + f0;

@@ -16,6 +16,8 @@ runs write equal files.
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 
 from ._blockio import check_input, flags_from, frames_u8, output, round_trip
@@ -23,7 +25,7 @@ from ._lib import VCF_DCT_NO_SUBBANDS, VCF_DCT_PERCEPTUAL, call
 from .device import DeviceBuffer, _h
 from .klt import shape_bin
 
-__all__ = ["padded_shape", "check_block_size", "shape_bin", "flags_from", "initial_weights", "moments_device",
+__all__ = ["padded_shape", "tile_plan", "check_block_size", "shape_bin", "flags_from", "initial_weights", "moments_device",
            "train_device", "encode_device", "decode_device", "moments", "train", "encode", "decode",
            "VCF_DCT_NO_SUBBANDS", "VCF_DCT_PERCEPTUAL"]
 
@@ -44,6 +46,15 @@ def padded_shape(H: int, W: int, block_size: int = 8):
     from . import klt
     check_block_size(block_size)
     return klt.padded_shape(H, W, block_size)
+
+
+def tile_plan(H: int, W: int, block_size: int = 8, decode: bool = False):
+    """(TB, lds_class, tiles, moment_chunks, moment_stage_blocks): the blocks of one encode (or
+    decode) workgroup, its LDS class 0..2 and the workgroups per frame; the moments kernel's
+    workgroups per frame and channel and the blocks one of them stages at a time.  Host only."""
+    v = [ctypes.c_int32() for _ in range(5)]
+    call("vcf_lbt_tile_plan", H, W, block_size, int(bool(decode)), *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
 
 
 def rows(H: int, W: int, B: int) -> int:
