@@ -25,56 +25,32 @@
 //            float32 rows W[k][j .. j + 7] are wave-uniform and widened, the sums, the
 //            inverse YCoCg and +128 are float64; clip, truncate, crop.
 //
+// The tiles, their LDS, the index maps and the loops that move a tile in and out are
+// vcf_block_tile.h's, shared with vcf_lbt.hip; the products and the moments kernel are here.
+//
 // Rounding contract ("2D-KLT"): the sums run over j (decode: k) ascending with
 // FMAs from zero; the encoder sums W[k][j] * s[j] and multiplies by 1/4 at the end, which
 // is bit-identical to summing W[k][j] * x[j] (a power-of-two scale commutes with every
 // rounding).  No result depends on the tile, the lane or the batch position.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "vcf_amd.h"
+#include "vcf_block_tile.h"
 #include "vcf_internal.h"
 
 namespace vcf {
 namespace {
 
-constexpr int kThreads = 512;      // encode / decode
-constexpr int kMomThreads = 256;   // moments
 constexpr int kMinB = 2, kMaxB = 16;
-constexpr int kMomChunk = 2048;    // blocks per workgroup: 2048 * 512 * 512 = 2^29 fits int32
-constexpr int kMomLds = 16384;     // int16 values of one staged tile
-
-struct KltGeom {
-    int H, W, Hp, Wp, top, left;
-    int B, D;
-    int nbx, nby, N;    // blocks per row / column / frame
-    int TB;             // blocks per workgroup tile (encode, decode)
-    long long rgb_stride, k_stride;
-};
-
-__device__ inline int align16(int x) { return (x + 15) & ~15; }
-
-// s = 4 x of channel c at padded position (py, px): zero pad, -128, YCoCg
-__device__ inline int sample4(const uint8_t *__restrict__ src, const KltGeom &g, int py, int px, int c)
-{
-    const int y = py - g.top, x = px - g.left;
-    int R = -128, G = -128, Bl = -128;
-    if (y >= 0 && y < g.H && x >= 0 && x < g.W) {
-        const uint8_t *p = src + ((long long)y * g.W + x) * 3;
-        R += p[0];
-        G += p[1];
-        Bl += p[2];
-    }
-    return c == 0 ? R + 2 * G + Bl : (c == 1 ? 2 * R - 2 * Bl : 2 * G - R - Bl);
-}
 
 // ---------------------------------------------------------------------------
-// moments
+// moments: int64 integer atomics, a matrix per channel.  The tiling is that of
+// vcf_block_tile.h's moments_tiles, kept here in full: through the shared body the compiler
+// orders this kernel's instructions otherwise, and at B = 16 it measured 0.8 % slower.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kMomThreads) void klt_moments_kernel(const uint8_t *__restrict__ rgb,
                                                                  unsigned long long *__restrict__ S1,
-                                                                 unsigned long long *__restrict__ S2, KltGeom g,
+                                                                 unsigned long long *__restrict__ S2, BlockGeom g,
                                                                  int nt, int T, int tbm)
 {
     __shared__ __attribute__((aligned(16))) short X[kMomLds];
@@ -159,33 +135,27 @@ __global__ __launch_bounds__(kMomThreads) void klt_moments_kernel(const uint8_t 
 // encode
 // ---------------------------------------------------------------------------
 template <int LDSB>
-__global__ __launch_bounds__(kThreads) void klt_encode_kernel(const uint8_t *__restrict__ rgb,
-                                                             uint8_t *__restrict__ kout,
-                                                             const double *__restrict__ wts, KltGeom g, double Qd,
-                                                             int sub)
+__global__ __launch_bounds__(kTileThreads) void klt_encode_kernel(const uint8_t *__restrict__ rgb,
+                                                                 uint8_t *__restrict__ kout,
+                                                                 const double *__restrict__ wts, BlockGeom g, double Qd,
+                                                                 int sub)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDSB];
-    const int D = g.D, B = g.B, TB = g.TB;
-    const int XS = D | 1;          // odd row stride of the int16 tile
-    const int OS = D * 3 + 4;      // row stride of the collected bytes
+    const int D = g.D, TB = g.TB;
+    const int XS = stage_stride(D), OS = out_stride(D);
     short *X = reinterpret_cast<short *>(smem);
-    uint8_t *O = smem + align16(TB * XS * 2);
+    uint8_t *O = smem + stage_bytes(g, 2);
 
     const int b0 = blockIdx.x * TB, tbv = min(TB, g.N - b0);
     const uint8_t *src = rgb + (long long)blockIdx.y * g.rgb_stride;
     uint8_t *dst = kout + (long long)blockIdx.y * g.k_stride;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kThreads >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kTileThreads >> 6;
     const int nkg = (D + 7) >> 3, nbc = (tbv + 63) >> 6;
 
     for (int c = 0; c < 3; ++c) {
         const double *Wc = wts + ((long long)blockIdx.y * 3 + c) * D * D;
-        for (int e = tid; e < tbv * D; e += kThreads) {
-            const int bl = e / D, d = e - bl * D;
-            const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-            const int ky = d / B, kx = d - ky * B;
-            X[bl * XS + d] = (short)sample4(src, g, by * B + ky, bx * B + kx, c);
-        }
+        stage_samples(src, X, g, b0, tbv, c, [](int v) { return (short)v; });
         __syncthreads();
         for (int it = wave; it < nbc * nkg; it += nw) {
             const int kg = it % nkg, bc = it / nkg;
@@ -224,25 +194,7 @@ __global__ __launch_bounds__(kThreads) void klt_encode_kernel(const uint8_t *__r
         }
         __syncthreads();   // X is staged again for the next channel
     }
-    const int total = tbv * D * 3;
-    if (!sub) {
-        // coefficient (ky, kx) of block (by, bx) at (by B + ky, bx B + kx): runs of 3 B bytes
-        for (int e = tid; e < total; e += kThreads) {
-            const int bl = e / (D * 3), q = e - bl * (D * 3);
-            const int k = q / 3, ky = k / B, kx = k - ky * B;
-            const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-            dst[((long long)(by * B + ky) * g.Wp + bx * B + kx) * 3 + (q - k * 3)] = O[bl * OS + q];
-        }
-    } else {
-        // subband (ky, kx) holds coefficient (ky, kx) of every block: runs of 3 bytes per block
-        for (int e = tid; e < total; e += kThreads) {
-            const int c = e % 3, t = e / 3;
-            const int k = t / tbv, bl = t - k * tbv;
-            const int ky = k / B, kx = k - ky * B;
-            const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-            dst[((long long)(ky * g.nby + by) * g.Wp + kx * g.nbx + bx) * 3 + c] = O[bl * OS + k * 3 + c];
-        }
-    }
+    scatter_indices(O, dst, g, b0, tbv, sub);
 }
 
 // ---------------------------------------------------------------------------
@@ -270,13 +222,13 @@ __device__ inline void klt_synth(const float *__restrict__ W0, const short *y0, 
 }
 
 template <int LDSB>
-__global__ __launch_bounds__(kThreads) void klt_decode_kernel(const uint8_t *__restrict__ kin,
-                                                             uint8_t *__restrict__ rgb,
-                                                             const float *__restrict__ wts, KltGeom g, int Q, int sub)
+__global__ __launch_bounds__(kTileThreads) void klt_decode_kernel(const uint8_t *__restrict__ kin,
+                                                                 uint8_t *__restrict__ rgb,
+                                                                 const float *__restrict__ wts, BlockGeom g, int Q, int sub)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDSB];
-    const int D = g.D, B = g.B, TB = g.TB;
-    const int XS = D | 1, OS = D * 3 + 4;
+    const int D = g.D, TB = g.TB;
+    const int XS = stage_stride(D), OS = out_stride(D);
     const int ys = align16(TB * XS * 2) / 2;   // one channel's int16 tile, in elements
     short *Y = reinterpret_cast<short *>(smem);
     uint8_t *O = smem + 3 * ys * 2;
@@ -286,29 +238,11 @@ __global__ __launch_bounds__(kThreads) void klt_decode_kernel(const uint8_t *__r
     uint8_t *dst = rgb + (long long)blockIdx.y * g.rgb_stride;
     const float *W0 = wts + (long long)blockIdx.y * 3 * D * D;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kThreads >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kTileThreads >> 6;
     const int njg = (D + 7) >> 3, nbc = (tbv + 63) >> 6;
 
     // u8 -> int16 - 128 -> Q k (int16, wrapping) -> block layout
-    for (int e = tid; e < tbv * D * 3; e += kThreads) {
-        int c, bl, k;
-        if (sub) {
-            c = e % 3;
-            const int t = e / 3;
-            k = t / tbv;
-            bl = t - k * tbv;
-        } else {
-            bl = e / (D * 3);
-            const int q = e - bl * (D * 3);
-            k = q / 3;
-            c = q - k * 3;
-        }
-        const int ky = k / B, kx = k - ky * B;
-        const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-        const long long at = sub ? ((long long)(ky * g.nby + by) * g.Wp + kx * g.nbx + bx)
-                                 : ((long long)(by * B + ky) * g.Wp + bx * B + kx);
-        Y[c * ys + bl * XS + k] = (short)(Q * ((int)src[at * 3 + c] - 128));
-    }
+    gather_indices(src, Y, ys, g, b0, tbv, sub, Q, [](short y, int, int) { return y; });
     __syncthreads();
     for (int it = wave; it < nbc * njg; it += nw) {
         const int jg = it % njg, bc = it / njg;
@@ -336,66 +270,24 @@ __global__ __launch_bounds__(kThreads) void klt_decode_kernel(const uint8_t *__r
         }
     }
     __syncthreads();
-    // crop: runs of 3 B bytes
-    for (int e = tid; e < tbv * D * 3; e += kThreads) {
-        const int bl = e / (D * 3), q = e - bl * (D * 3);
-        const int j = q / 3, ky = j / B, kx = j - ky * B;
-        const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-        const int y = by * B + ky - g.top, x = bx * B + kx - g.left;
-        if (y < 0 || y >= g.H || x < 0 || x >= g.W) continue;
-        dst[((long long)y * g.W + x) * 3 + (q - j * 3)] = O[bl * OS + q];
-    }
+    crop_pixels(O, dst, g, b0, tbv);
 }
 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-constexpr int kLds[3] = {48 * 1024, 80 * 1024, 156 * 1024};   // 3, 2, 1 workgroups per CU (160 KiB LDS)
-
-void make_geom(int32_t H, int32_t W, int32_t B, KltGeom &g)
-{
-    g.H = H;
-    g.W = W;
-    g.B = B;
-    g.D = B * B;
-    g.Hp = (H + B - 1) / B * B;
-    g.Wp = (W + B - 1) / B * B;
-    g.top = (g.Hp - H) / 2;
-    g.left = (g.Wp - W) / 2;
-    g.nbx = g.Wp / B;
-    g.nby = g.Hp / B;
-    g.N = g.nbx * g.nby;
-    // a tile of about 8192 values (16384 where a block alone has more than 128), whole waves of blocks
-    const int budget = g.D > 128 ? 16384 : 8192;
-    g.TB = std::min(1024, std::max(64, budget / g.D / 64 * 64));
-    g.rgb_stride = (long long)H * W * 3;
-    g.k_stride = (long long)g.Hp * g.Wp * 3;
-}
-
-long long a16(long long x) { return (x + 15) & ~15LL; }
-long long enc_lds(const KltGeom &g) { return a16((long long)g.TB * (g.D | 1) * 2) + (long long)g.TB * (g.D * 3 + 4); }
-long long dec_lds(const KltGeom &g) { return 3 * a16((long long)g.TB * (g.D | 1) * 2) + (long long)g.TB * (g.D * 3 + 4); }
-
-int lds_class(long long bytes)
-{
-    for (int c = 0; c < 3; ++c)
-        if (bytes <= kLds[c]) return c;
-    return -1;
-}
-
 int check_shape(int32_t H, int32_t W, int32_t B)
 {
     if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad shape %d x %d", H, W);
     if (B > kMaxB) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: the KLT kernels cover 2 <= B <= 16", B);
     if (B < kMinB)
         return set_error(VCF_ERR_INVALID, "block size %d: blocks of one sample have no covariance matrix", B);
-    // the kernels address within a frame with 32-bit arithmetic
-    if (((long long)H + B) * ((long long)W + B) * 3 >= (1LL << 31)) return set_error(VCF_ERR_INVALID, "frame too large");
+    if (!frame_fits_int32(H, W, B)) return set_error(VCF_ERR_INVALID, "frame too large");
     return VCF_OK;
 }
 
 int check_args(const void *a, const void *b, const void *c, int64_t n_frames, int32_t H, int32_t W, int32_t B,
-               int32_t Q, uint32_t flags, KltGeom &g)
+               int32_t Q, uint32_t flags, BlockGeom &g)
 {
     if (!a || !b || !c) return set_error(VCF_ERR_INVALID, "null buffer");
     if (n_frames < 1) return set_error(VCF_ERR_INVALID, "n_frames < 1");
@@ -403,7 +295,7 @@ int check_args(const void *a, const void *b, const void *c, int64_t n_frames, in
     if (rc != VCF_OK) return rc;
     if (Q < 1 || Q > 32767) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if (flags & ~VCF_DCT_NO_SUBBANDS) return set_error(VCF_ERR_INVALID, "unknown flags 0x%x", flags);
-    make_geom(H, W, B, g);
+    g = make_block_geom(H, W, B);
     if (g.N < 2) return set_error(VCF_ERR_INVALID, "a frame of one block has no covariance matrix");
     return VCF_OK;
 }
@@ -421,8 +313,7 @@ int vcf_klt_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp, 
     if (!Hp || !Wp || !pad_top || !pad_left) return set_error(VCF_ERR_INVALID, "null pointer");
     const int rc = check_shape(H, W, block_size);
     if (rc != VCF_OK) return rc;
-    KltGeom g;
-    make_geom(H, W, block_size, g);
+    const BlockGeom g = make_block_geom(H, W, block_size);
     *Hp = g.Hp;
     *Wp = g.Wp;
     *pad_top = g.top;
@@ -433,7 +324,7 @@ int vcf_klt_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp, 
 int vcf_klt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                     int64_t *s1_dev, int64_t *s2_dev, void *stream)
 {
-    KltGeom g;
+    BlockGeom g;
     int rc = check_args(rgb_dev, s1_dev, s2_dev, n_frames, H, W, block_size, 1, 0, g);
     if (rc != VCF_OK) return rc;
     const long long D = g.D;
@@ -442,74 +333,50 @@ int vcf_klt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t
     rc = hip_check(hipMemsetAsync(s2_dev, 0, (size_t)(n_frames * 3 * D * D * 8), (hipStream_t)stream),
                    "hipMemsetAsync(S2)");
     if (rc != VCF_OK) return rc;
-    const int nt = (g.D + 7) / 8, T = nt * (nt + 1) / 2;
-    const int tbm = std::min(kMomChunk, kMomLds / (nt * 8));
-    const unsigned chunks = (unsigned)((g.N + kMomChunk - 1) / kMomChunk);
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid(chunks, 3, (unsigned)std::min<int64_t>(65535, n_frames - f0));
-        hipLaunchKernelGGL(klt_moments_kernel, grid, dim3(kMomThreads), 0, (hipStream_t)stream,
+    const BlockPlan p = make_block_plan(g, false, 2);
+    return for_frame_chunks(n_frames, "klt_moments_kernel launch", [&](int64_t f0, unsigned nf) {
+        hipLaunchKernelGGL(klt_moments_kernel, dim3((unsigned)p.chunks, 3, nf), dim3(kMomThreads), 0, (hipStream_t)stream,
                            rgb_dev + f0 * g.rgb_stride, (unsigned long long *)s1_dev + f0 * 3 * D,
-                           (unsigned long long *)s2_dev + f0 * 3 * D * D, g, nt, T, tbm);
-        rc = hip_check(hipGetLastError(), "klt_moments_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+                           (unsigned long long *)s2_dev + f0 * 3 * D * D, g, p.nt, p.T, p.tbm);
+    });
 }
 
 int vcf_klt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const double *weights_f64_dev, uint8_t *k_dev, void *stream)
 {
-    KltGeom g;
-    int rc = check_args(rgb_dev, weights_f64_dev, k_dev, n_frames, H, W, block_size, Q, flags, g);
+    BlockGeom g;
+    const int rc = check_args(rgb_dev, weights_f64_dev, k_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
-    const int cls = lds_class(enc_lds(g));
-    if (cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
+    const BlockPlan p = make_block_plan(g, false, 2);
+    if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;
     const long long DD = (long long)g.D * g.D;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)((g.N + g.TB - 1) / g.TB), (unsigned)std::min<int64_t>(65535, n_frames - f0));
-        const uint8_t *in = rgb_dev + f0 * g.rgb_stride;
-        const double *w = weights_f64_dev + f0 * 3 * DD;
-        uint8_t *out = k_dev + f0 * g.k_stride;
-#define VCF_KLT_ENC(C)                                                                                          \
-        hipLaunchKernelGGL((klt_encode_kernel<kLds[C]>), grid, dim3(kThreads), 0, (hipStream_t)stream, in, out, \
-                           w, g, (double)Q, sub)
-        if (cls == 0) VCF_KLT_ENC(0);
-        else if (cls == 1) VCF_KLT_ENC(1);
-        else VCF_KLT_ENC(2);
-#undef VCF_KLT_ENC
-        rc = hip_check(hipGetLastError(), "klt_encode_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    return for_frame_chunks(n_frames, "klt_encode_kernel launch", [&](int64_t f0, unsigned nf) {
+        with_lds_class(p.cls, [&](auto lds) {
+            hipLaunchKernelGGL((klt_encode_kernel<decltype(lds)::value>), dim3((unsigned)p.tiles, nf), dim3(kTileThreads),
+                               0, (hipStream_t)stream, rgb_dev + f0 * g.rgb_stride, k_dev + f0 * g.k_stride,
+                               weights_f64_dev + f0 * 3 * DD, g, (double)Q, sub);
+        });
+    });
 }
 
 int vcf_klt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const float *weights_f32_dev, uint8_t *rgb_dev, void *stream)
 {
-    KltGeom g;
-    int rc = check_args(k_dev, weights_f32_dev, rgb_dev, n_frames, H, W, block_size, Q, flags, g);
+    BlockGeom g;
+    const int rc = check_args(k_dev, weights_f32_dev, rgb_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
-    const int cls = lds_class(dec_lds(g));
-    if (cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
+    const BlockPlan p = make_block_plan(g, true, 2);
+    if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;
     const long long DD = (long long)g.D * g.D;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)((g.N + g.TB - 1) / g.TB), (unsigned)std::min<int64_t>(65535, n_frames - f0));
-        const uint8_t *in = k_dev + f0 * g.k_stride;
-        const float *w = weights_f32_dev + f0 * 3 * DD;
-        uint8_t *out = rgb_dev + f0 * g.rgb_stride;
-#define VCF_KLT_DEC(C)                                                                                          \
-        hipLaunchKernelGGL((klt_decode_kernel<kLds[C]>), grid, dim3(kThreads), 0, (hipStream_t)stream, in, out, \
-                           w, g, (int)Q, sub)
-        if (cls == 0) VCF_KLT_DEC(0);
-        else if (cls == 1) VCF_KLT_DEC(1);
-        else VCF_KLT_DEC(2);
-#undef VCF_KLT_DEC
-        rc = hip_check(hipGetLastError(), "klt_decode_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    return for_frame_chunks(n_frames, "klt_decode_kernel launch", [&](int64_t f0, unsigned nf) {
+        with_lds_class(p.cls, [&](auto lds) {
+            hipLaunchKernelGGL((klt_decode_kernel<decltype(lds)::value>), dim3((unsigned)p.tiles, nf), dim3(kTileThreads),
+                               0, (hipStream_t)stream, k_dev + f0 * g.k_stride, rgb_dev + f0 * g.rgb_stride,
+                               weights_f32_dev + f0 * 3 * DD, g, (int)Q, sub);
+        });
+    });
 }
 
 }  // extern "C"

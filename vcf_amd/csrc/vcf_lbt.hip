@@ -5,7 +5,7 @@
 //   moments  S1 = sum x, S2 = sum x x^T over the 3 N blocks of a frame (the three YCoCg
 //            channels pooled), x the D = B * B values of a block after the centred zero
 //            pad and -128.  The kernel works on s = 4 x (integers, |s| <= 512) with int32
-//            partial sums over at most 2048 blocks, as vcf_klt_moments does, and adds
+//            partial sums over at most 2048 blocks (vcf_block_tile.h's moments_tiles) and adds
 //            them to the float64 results with atomics: every partial and every total is
 //            an integer below 2^53 (scaled by the exact 1/4 and 1/16), so the float64
 //            sums are exact in any order.
@@ -15,8 +15,8 @@
 //            v_mfma_f32_32x32x2_f32, one 32 x 32 output tile per wave.  C, S, both weight
 //            matrices and three scratch matrices live in LDS (7 x 16.25 KiB); the Adam
 //            moments and the gradients live in registers in the MFMA output layout.
-//   encode   the vcf_klt_dz_encode tiling in float32: a workgroup owns TB blocks, a lane a
-//            block, a work item 8 coefficients; rows of We are wave-uniform.
+//   encode   vcf_block_tile.h's tiles, as vcf_klt_dz.hip, in float32: a workgroup owns TB blocks,
+//            a lane a block, a work item 8 coefficients; rows of We are wave-uniform.
 //   decode   likewise, with the stored float32 decoder matrix.
 //
 // Training in moment form.  X: the 3 N x D blocks minus the scalar mean mu, C = X^T X / rows,
@@ -33,31 +33,18 @@
 // position.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "vcf_amd.h"
+#include "vcf_block_tile.h"
 #include "vcf_internal.h"
 
 namespace vcf {
 namespace {
 
-constexpr int kThreads = 512;      // encode / decode
-constexpr int kMomThreads = 256;   // moments
 constexpr int kTrainThreads = 256; // train: one wave per SIMD
 constexpr int kMinB = 2, kMaxB = 8;
-constexpr int kMomChunk = 2048;    // blocks per workgroup: 2048 * 512 * 512 = 2^29 fits int32
-constexpr int kMomLds = 16384;     // int16 values of one staged tile
 constexpr int kDP = 64;            // the training matrices' padded dimension
 constexpr int kLD = 65;            // and their LDS row stride (odd: column reads hit 32 banks)
 constexpr int kMat = kDP * kLD;
-
-struct LbtGeom {
-    int H, W, Hp, Wp, top, left;
-    int B, D;
-    int nbx, nby, N;    // blocks per row / column / frame and channel
-    int TB;             // blocks per workgroup tile (encode, decode)
-    long long rgb_stride, k_stride;
-};
 
 // -p: Y_QSSs / 121 and C_QSSs / 99 (float64) per coefficient
 struct LbtScale {
@@ -65,105 +52,18 @@ struct LbtScale {
     double t[2][kDP];
 };
 
-__device__ inline int align16(int x) { return (x + 15) & ~15; }
-
-// s = 4 x of channel c at padded position (py, px): zero pad, -128, YCoCg
-__device__ inline int sample4(const uint8_t *__restrict__ src, const LbtGeom &g, int py, int px, int c)
-{
-    const int y = py - g.top, x = px - g.left;
-    int R = -128, G = -128, Bl = -128;
-    if (y >= 0 && y < g.H && x >= 0 && x < g.W) {
-        const uint8_t *p = src + ((long long)y * g.W + x) * 3;
-        R += p[0];
-        G += p[1];
-        Bl += p[2];
-    }
-    return c == 0 ? R + 2 * G + Bl : (c == 1 ? 2 * R - 2 * Bl : 2 * G - R - Bl);
-}
-
 // ---------------------------------------------------------------------------
-// moments (vcf_klt_moments' tiling; the three channels add into one matrix)
+// moments: float64 atomics of the exact 1/4 and 1/16; the three channels add into one matrix
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kMomThreads) void lbt_moments_kernel(const uint8_t *__restrict__ rgb,
                                                                  double *__restrict__ S1, double *__restrict__ S2,
-                                                                 LbtGeom g, int nt, int T, int tbm)
+                                                                 BlockGeom g, int nt, int T, int tbm)
 {
-    __shared__ __attribute__((aligned(16))) short X[kMomLds];
-    const int D = g.D, B = g.B, DP = nt * 8;
-    const int c = blockIdx.y, tid = threadIdx.x;
-    const uint8_t *src = rgb + (long long)blockIdx.z * g.rgb_stride;
-    double *s1 = S1 + (long long)blockIdx.z * D;
-    double *s2 = S2 + (long long)blockIdx.z * D * D;
-    const int b_lo = blockIdx.x * kMomChunk, b_hi = min(g.N, b_lo + kMomChunk);
-    const int tpp = min(T, kMomThreads), Z = kMomThreads / tpp;   // tiles per pass, block slices
-    const int tl = tid % tpp, z = tid / tpp;
-
-    for (int p0 = 0; p0 < T; p0 += tpp) {
-        const int t = p0 + tl;
-        const bool active = t < T && z < Z;
-        // tile t of the upper triangle, row-major: (ti, tj), ti <= tj
-        int ti = 0, rem = min(t, T - 1);
-        while (rem >= nt - ti) {
-            rem -= nt - ti;
-            ++ti;
-        }
-        const int tj = ti + rem;
-        int acc[8][8], a1[8];
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-            a1[a] = 0;
-#pragma unroll
-            for (int b = 0; b < 8; ++b) acc[a][b] = 0;
-        }
-        for (int t0 = b_lo; t0 < b_hi; t0 += tbm) {
-            const int nb = min(tbm, b_hi - t0);
-            __syncthreads();
-            for (int e = tid; e < nb * DP; e += kMomThreads) {
-                const int bl = e / DP, d = e - bl * DP;
-                int v = 0;
-                if (d < D) {
-                    const int b = t0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-                    const int ky = d / B, kx = d - ky * B;
-                    v = sample4(src, g, by * B + ky, bx * B + kx, c);
-                }
-                X[e] = (short)v;
-            }
-            __syncthreads();
-            if (active) {
-                for (int bl = z; bl < nb; bl += Z) {
-                    const short *r = X + bl * DP;
-                    int si[8], sj[8];
-#pragma unroll
-                    for (int a = 0; a < 8; ++a) {
-                        si[a] = r[ti * 8 + a];
-                        sj[a] = r[tj * 8 + a];
-                    }
-#pragma unroll
-                    for (int a = 0; a < 8; ++a) {
-                        a1[a] += si[a];
-#pragma unroll
-                        for (int b = 0; b < 8; ++b) acc[a][b] += si[a] * sj[b];
-                    }
-                }
-            }
-        }
-        if (active) {
-#pragma unroll
-            for (int a = 0; a < 8; ++a) {
-                const int i = ti * 8 + a;
-                if (i >= D) continue;
-                if (ti == tj) atomicAdd(s1 + i, (double)a1[a] * 0.25);
-#pragma unroll
-                for (int b = 0; b < 8; ++b) {
-                    const int j = tj * 8 + b;
-                    if (j >= D) continue;
-                    const double v = (double)acc[a][b] * 0.0625;
-                    atomicAdd(s2 + (long long)i * D + j, v);
-                    if (ti != tj) atomicAdd(s2 + (long long)j * D + i, v);
-                }
-            }
-        }
-    }
+    const int D = g.D;
+    moments_tiles(rgb + (long long)blockIdx.z * g.rgb_stride, S1 + (long long)blockIdx.z * D,
+                  S2 + (long long)blockIdx.z * D * D, g, nt, T, tbm, blockIdx.x, blockIdx.y,
+                  // v sums s = 4 x (S1) or s s^T = 16 x x^T (S2): the exact 1/4 and 1/16 give the sums of x
+                  [](int v, bool first) { return (double)v * (first ? 0.25 : 0.0625); });
 }
 
 // ---------------------------------------------------------------------------
@@ -337,18 +237,17 @@ __global__ __launch_bounds__(kTrainThreads) void lbt_train_kernel(const double *
 // encode
 // ---------------------------------------------------------------------------
 template <int LDSB>
-__global__ __launch_bounds__(kThreads) void lbt_encode_kernel(const uint8_t *__restrict__ rgb,
-                                                             uint8_t *__restrict__ kout,
-                                                             const float *__restrict__ wts,
-                                                             const float *__restrict__ means, LbtGeom g, float Qf,
-                                                             int sub, LbtScale pq)
+__global__ __launch_bounds__(kTileThreads) void lbt_encode_kernel(const uint8_t *__restrict__ rgb,
+                                                                 uint8_t *__restrict__ kout,
+                                                                 const float *__restrict__ wts,
+                                                                 const float *__restrict__ means, BlockGeom g, float Qf,
+                                                                 int sub, LbtScale pq)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDSB];
-    const int D = g.D, B = g.B, TB = g.TB;
-    const int XS = D | 1;          // odd row stride of the float tile
-    const int OS = D * 3 + 4;      // row stride of the collected bytes
+    const int D = g.D, TB = g.TB;
+    const int XS = stage_stride(D), OS = out_stride(D);
     float *X = reinterpret_cast<float *>(smem);
-    uint8_t *O = smem + align16(TB * XS * 4);
+    uint8_t *O = smem + stage_bytes(g, 4);
 
     const int b0 = blockIdx.x * TB, tbv = min(TB, g.N - b0);
     const uint8_t *src = rgb + (long long)blockIdx.y * g.rgb_stride;
@@ -356,16 +255,11 @@ __global__ __launch_bounds__(kThreads) void lbt_encode_kernel(const uint8_t *__r
     const float *Wf = wts + (long long)blockIdx.y * D * D;
     const float mu = means[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kThreads >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kTileThreads >> 6;
     const int nkg = (D + 7) >> 3, nbc = (tbv + 63) >> 6;
 
     for (int c = 0; c < 3; ++c) {
-        for (int e = tid; e < tbv * D; e += kThreads) {
-            const int bl = e / D, d = e - bl * D;
-            const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-            const int ky = d / B, kx = d - ky * B;
-            X[bl * XS + d] = (float)sample4(src, g, by * B + ky, bx * B + kx, c) * 0.25f - mu;
-        }
+        stage_samples(src, X, g, b0, tbv, c, [mu](int v) { return (float)v * 0.25f - mu; });
         __syncthreads();
         for (int it = wave; it < nbc * nkg; it += nw) {
             const int kg = it % nkg, bc = it / nkg;
@@ -394,23 +288,7 @@ __global__ __launch_bounds__(kThreads) void lbt_encode_kernel(const uint8_t *__r
         }
         __syncthreads();   // X is staged again for the next channel
     }
-    const int total = tbv * D * 3;
-    if (!sub) {
-        for (int e = tid; e < total; e += kThreads) {
-            const int bl = e / (D * 3), q = e - bl * (D * 3);
-            const int k = q / 3, ky = k / B, kx = k - ky * B;
-            const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-            dst[((long long)(by * B + ky) * g.Wp + bx * B + kx) * 3 + (q - k * 3)] = O[bl * OS + q];
-        }
-    } else {
-        for (int e = tid; e < total; e += kThreads) {
-            const int c = e % 3, t = e / 3;
-            const int k = t / tbv, bl = t - k * tbv;
-            const int ky = k / B, kx = k - ky * B;
-            const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-            dst[((long long)(ky * g.nby + by) * g.Wp + kx * g.nbx + bx) * 3 + c] = O[bl * OS + k * 3 + c];
-        }
-    }
+    scatter_indices(O, dst, g, b0, tbv, sub);
 }
 
 // ---------------------------------------------------------------------------
@@ -438,15 +316,15 @@ __device__ inline void lbt_synth(const float *__restrict__ Wf, const short *y0, 
 }
 
 template <int LDSB>
-__global__ __launch_bounds__(kThreads) void lbt_decode_kernel(const uint8_t *__restrict__ kin,
-                                                             uint8_t *__restrict__ rgb,
-                                                             const float *__restrict__ wts,
-                                                             const float *__restrict__ means, LbtGeom g, int Q,
-                                                             int sub, LbtScale pq)
+__global__ __launch_bounds__(kTileThreads) void lbt_decode_kernel(const uint8_t *__restrict__ kin,
+                                                                 uint8_t *__restrict__ rgb,
+                                                                 const float *__restrict__ wts,
+                                                                 const float *__restrict__ means, BlockGeom g, int Q,
+                                                                 int sub, LbtScale pq)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDSB];
-    const int D = g.D, B = g.B, TB = g.TB;
-    const int XS = D | 1, OS = D * 3 + 4;
+    const int D = g.D, TB = g.TB;
+    const int XS = stage_stride(D), OS = out_stride(D);
     const int ys = align16(TB * XS * 2) / 2;   // one channel's int16 tile, in elements
     short *Y = reinterpret_cast<short *>(smem);
     uint8_t *O = smem + 3 * ys * 2;
@@ -457,31 +335,14 @@ __global__ __launch_bounds__(kThreads) void lbt_decode_kernel(const uint8_t *__r
     const float *Wf = wts + (long long)blockIdx.y * D * D;
     const float mu = means[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kThreads >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = kTileThreads >> 6;
     const int njg = (D + 7) >> 3, nbc = (tbv + 63) >> 6;
 
     // u8 -> int16 - 128 -> Q k (int16, wrapping) [-> / the -p weight, back into int16] -> block layout
-    for (int e = tid; e < tbv * D * 3; e += kThreads) {
-        int c, bl, k;
-        if (sub) {
-            c = e % 3;
-            const int t = e / 3;
-            k = t / tbv;
-            bl = t - k * tbv;
-        } else {
-            bl = e / (D * 3);
-            const int q = e - bl * (D * 3);
-            k = q / 3;
-            c = q - k * 3;
-        }
-        const int ky = k / B, kx = k - ky * B;
-        const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-        const long long at = sub ? ((long long)(ky * g.nby + by) * g.Wp + kx * g.nbx + bx)
-                                 : ((long long)(by * B + ky) * g.Wp + bx * B + kx);
-        short y16 = (short)(Q * ((int)src[at * 3 + c] - 128));
+    gather_indices(src, Y, ys, g, b0, tbv, sub, Q, [&pq](short y16, int c, int k) {
         if (pq.on) y16 = (short)(int)((double)y16 / pq.t[c ? 1 : 0][k]);   // :518-526
-        Y[c * ys + bl * XS + k] = y16;
-    }
+        return y16;
+    });
     __syncthreads();
     for (int it = wave; it < nbc * njg; it += nw) {
         const int jg = it % njg, bc = it / njg;
@@ -509,86 +370,23 @@ __global__ __launch_bounds__(kThreads) void lbt_decode_kernel(const uint8_t *__r
         }
     }
     __syncthreads();
-    // crop: runs of 3 B bytes
-    for (int e = tid; e < tbv * D * 3; e += kThreads) {
-        const int bl = e / (D * 3), q = e - bl * (D * 3);
-        const int j = q / 3, ky = j / B, kx = j - ky * B;
-        const int b = b0 + bl, by = b / g.nbx, bx = b - by * g.nbx;
-        const int y = by * B + ky - g.top, x = bx * B + kx - g.left;
-        if (y < 0 || y >= g.H || x < 0 || x >= g.W) continue;
-        dst[((long long)y * g.W + x) * 3 + (q - j * 3)] = O[bl * OS + q];
-    }
+    crop_pixels(O, dst, g, b0, tbv);
 }
 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-constexpr int kLds[3] = {48 * 1024, 80 * 1024, 156 * 1024};   // 3, 2, 1 workgroups per CU (160 KiB LDS)
-
-void make_geom(int32_t H, int32_t W, int32_t B, LbtGeom &g)
-{
-    g.H = H;
-    g.W = W;
-    g.B = B;
-    g.D = B * B;
-    g.Hp = (H + B - 1) / B * B;
-    g.Wp = (W + B - 1) / B * B;
-    g.top = (g.Hp - H) / 2;
-    g.left = (g.Wp - W) / 2;
-    g.nbx = g.Wp / B;
-    g.nby = g.Hp / B;
-    g.N = g.nbx * g.nby;
-    // a tile of about 8192 values, whole waves of blocks
-    g.TB = std::min(1024, std::max(64, 8192 / g.D / 64 * 64));
-    g.rgb_stride = (long long)H * W * 3;
-    g.k_stride = (long long)g.Hp * g.Wp * 3;
-}
-
-long long a16(long long x) { return (x + 15) & ~15LL; }
-long long enc_lds(const LbtGeom &g) { return a16((long long)g.TB * (g.D | 1) * 4) + (long long)g.TB * (g.D * 3 + 4); }
-long long dec_lds(const LbtGeom &g) { return 3 * a16((long long)g.TB * (g.D | 1) * 2) + (long long)g.TB * (g.D * 3 + 4); }
-
-int lds_class(long long bytes)
-{
-    for (int c = 0; c < 3; ++c)
-        if (bytes <= kLds[c]) return c;
-    return -1;
-}
-
-// What the launches use, and what vcf_lbt_tile_plan reports: the encode (or decode) grid and LDS
-// class, and the moments kernel's chunks per frame and blocks per staged tile.
-struct LbtPlan {
-    int cls;       // index into kLds, -1: the tile does not fit
-    int tiles;     // encode / decode workgroups per frame
-    int nt, T;     // moments: 8-wide coefficient groups, and their upper-triangle pairs
-    int chunks;    // moments: workgroups per frame and channel
-    int tbm;       // moments: blocks staged in LDS at a time
-};
-
-LbtPlan make_plan(const LbtGeom &g, bool decode)
-{
-    LbtPlan p;
-    p.cls = lds_class(decode ? dec_lds(g) : enc_lds(g));
-    p.tiles = (g.N + g.TB - 1) / g.TB;
-    p.nt = (g.D + 7) / 8;
-    p.T = p.nt * (p.nt + 1) / 2;
-    p.chunks = (g.N + kMomChunk - 1) / kMomChunk;
-    p.tbm = std::min(kMomChunk, kMomLds / (p.nt * 8));
-    return p;
-}
-
 int check_shape(int32_t H, int32_t W, int32_t B)
 {
     if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad shape %d x %d", H, W);
     if (B < kMinB || B > kMaxB)
         return set_error(VCF_ERR_UNSUPPORTED, "block size %d: the LBT kernels cover 2 <= B <= 8", B);
-    // the kernels address within a frame with 32-bit arithmetic
-    if (((long long)H + B) * ((long long)W + B) * 3 >= (1LL << 31)) return set_error(VCF_ERR_INVALID, "frame too large");
+    if (!frame_fits_int32(H, W, B)) return set_error(VCF_ERR_INVALID, "frame too large");
     return VCF_OK;
 }
 
 int check_args(const void *a, const void *b, const void *c, int64_t n_frames, int32_t H, int32_t W, int32_t B,
-               int32_t Q, uint32_t flags, LbtGeom &g)
+               int32_t Q, uint32_t flags, BlockGeom &g)
 {
     if (!a || !b || !c) return set_error(VCF_ERR_INVALID, "null buffer");
     if (n_frames < 1) return set_error(VCF_ERR_INVALID, "n_frames < 1");
@@ -596,7 +394,7 @@ int check_args(const void *a, const void *b, const void *c, int64_t n_frames, in
     if (rc != VCF_OK) return rc;
     if (Q < 1 || Q > 32767) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if (flags & ~(VCF_DCT_NO_SUBBANDS | VCF_DCT_PERCEPTUAL)) return set_error(VCF_ERR_INVALID, "unknown flags 0x%x", flags);
-    make_geom(H, W, B, g);
+    g = make_block_geom(H, W, B);
     return VCF_OK;
 }
 
@@ -629,9 +427,8 @@ int vcf_lbt_tile_plan(int32_t H, int32_t W, int32_t block_size, int32_t decode, 
         return set_error(VCF_ERR_INVALID, "null pointer");
     const int rc = check_shape(H, W, block_size);
     if (rc != VCF_OK) return rc;
-    LbtGeom g;
-    make_geom(H, W, block_size, g);
-    const LbtPlan p = make_plan(g, decode != 0);
+    const BlockGeom g = make_block_geom(H, W, block_size);
+    const BlockPlan p = make_block_plan(g, decode != 0, 4);
     if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     *TB = g.TB;
     *lds_class = p.cls;
@@ -644,7 +441,7 @@ int vcf_lbt_tile_plan(int32_t H, int32_t W, int32_t block_size, int32_t decode, 
 int vcf_lbt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                     double *s1_dev, double *s2_dev, void *stream)
 {
-    LbtGeom g;
+    BlockGeom g;
     int rc = check_args(rgb_dev, s1_dev, s2_dev, n_frames, H, W, block_size, 1, 0, g);
     if (rc != VCF_OK) return rc;
     const long long D = g.D;
@@ -652,15 +449,11 @@ int vcf_lbt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t
     if (rc != VCF_OK) return rc;
     rc = hip_check(hipMemsetAsync(s2_dev, 0, (size_t)(n_frames * D * D * 8), (hipStream_t)stream), "hipMemsetAsync(S2)");
     if (rc != VCF_OK) return rc;
-    const LbtPlan p = make_plan(g, false);
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)p.chunks, 3, (unsigned)std::min<int64_t>(65535, n_frames - f0));
-        hipLaunchKernelGGL(lbt_moments_kernel, grid, dim3(kMomThreads), 0, (hipStream_t)stream,
+    const BlockPlan p = make_block_plan(g, false, 4);
+    return for_frame_chunks(n_frames, "lbt_moments_kernel launch", [&](int64_t f0, unsigned nf) {
+        hipLaunchKernelGGL(lbt_moments_kernel, dim3((unsigned)p.chunks, 3, nf), dim3(kMomThreads), 0, (hipStream_t)stream,
                            rgb_dev + f0 * g.rgb_stride, s1_dev + f0 * D, s2_dev + f0 * D * D, g, p.nt, p.T, p.tbm);
-        rc = hip_check(hipGetLastError(), "lbt_moments_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    });
 }
 
 int vcf_lbt_train(const double *s1_dev, const double *s2_dev, int64_t n_frames, int32_t block_size, int64_t rows,
@@ -676,83 +469,57 @@ int vcf_lbt_train(const double *s1_dev, const double *s2_dev, int64_t n_frames, 
     if (epochs < 0) return set_error(VCF_ERR_INVALID, "epochs < 0");
     if (!(lr > 0.0) || !(lambda >= 0.0)) return set_error(VCF_ERR_INVALID, "lr must be > 0 and lambda >= 0");
     const long long D = block_size * block_size;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)std::min<int64_t>(65535, n_frames - f0));
-        hipLaunchKernelGGL(lbt_train_kernel, grid, dim3(kTrainThreads), 0, (hipStream_t)stream, s1_dev + f0 * D,
+    return for_frame_chunks(n_frames, "lbt_train_kernel launch", [&](int64_t f0, unsigned nf) {
+        hipLaunchKernelGGL(lbt_train_kernel, dim3(nf), dim3(kTrainThreads), 0, (hipStream_t)stream, s1_dev + f0 * D,
                            s2_dev + f0 * D * D, we_dev + f0 * D * D, wd_dev + f0 * D * D, mean_dev + f0,
                            loss_dev + f0 * 3, (int)D, (double)rows, (int)epochs, lr, (float)lambda);
-        const int rc = hip_check(hipGetLastError(), "lbt_train_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    });
 }
 
 int vcf_lbt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const float *we_dev, const float *mean_dev, uint8_t *k_dev, void *stream)
 {
-    LbtGeom g;
+    BlockGeom g;
     int rc = check_args(rgb_dev, we_dev, k_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
     if (!mean_dev) return set_error(VCF_ERR_INVALID, "null buffer");
     LbtScale pq;
     rc = make_scale(block_size, flags, pq);
     if (rc != VCF_OK) return rc;
-    const LbtPlan p = make_plan(g, false);
-    const int cls = p.cls;
-    if (cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
+    const BlockPlan p = make_block_plan(g, false, 4);
+    if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;
     const long long DD = (long long)g.D * g.D;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)p.tiles, (unsigned)std::min<int64_t>(65535, n_frames - f0));
-        const uint8_t *in = rgb_dev + f0 * g.rgb_stride;
-        const float *w = we_dev + f0 * DD;
-        const float *m = mean_dev + f0;
-        uint8_t *out = k_dev + f0 * g.k_stride;
-#define VCF_LBT_ENC(C)                                                                                          \
-        hipLaunchKernelGGL((lbt_encode_kernel<kLds[C]>), grid, dim3(kThreads), 0, (hipStream_t)stream, in, out, \
-                           w, m, g, (float)Q, sub, pq)
-        if (cls == 0) VCF_LBT_ENC(0);
-        else if (cls == 1) VCF_LBT_ENC(1);
-        else VCF_LBT_ENC(2);
-#undef VCF_LBT_ENC
-        rc = hip_check(hipGetLastError(), "lbt_encode_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    return for_frame_chunks(n_frames, "lbt_encode_kernel launch", [&](int64_t f0, unsigned nf) {
+        with_lds_class(p.cls, [&](auto lds) {
+            hipLaunchKernelGGL((lbt_encode_kernel<decltype(lds)::value>), dim3((unsigned)p.tiles, nf), dim3(kTileThreads),
+                               0, (hipStream_t)stream, rgb_dev + f0 * g.rgb_stride, k_dev + f0 * g.k_stride,
+                               we_dev + f0 * DD, mean_dev + f0, g, (float)Q, sub, pq);
+        });
+    });
 }
 
 int vcf_lbt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const float *wd_dev, const float *mean_dev, uint8_t *rgb_dev, void *stream)
 {
-    LbtGeom g;
+    BlockGeom g;
     int rc = check_args(k_dev, wd_dev, rgb_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
     if (!mean_dev) return set_error(VCF_ERR_INVALID, "null buffer");
     LbtScale pq;
     rc = make_scale(block_size, flags, pq);
     if (rc != VCF_OK) return rc;
-    const LbtPlan p = make_plan(g, true);
-    const int cls = p.cls;
-    if (cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
+    const BlockPlan p = make_block_plan(g, true, 4);
+    if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;
     const long long DD = (long long)g.D * g.D;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid((unsigned)p.tiles, (unsigned)std::min<int64_t>(65535, n_frames - f0));
-        const uint8_t *in = k_dev + f0 * g.k_stride;
-        const float *w = wd_dev + f0 * DD;
-        const float *m = mean_dev + f0;
-        uint8_t *out = rgb_dev + f0 * g.rgb_stride;
-#define VCF_LBT_DEC(C)                                                                                          \
-        hipLaunchKernelGGL((lbt_decode_kernel<kLds[C]>), grid, dim3(kThreads), 0, (hipStream_t)stream, in, out, \
-                           w, m, g, (int)Q, sub, pq)
-        if (cls == 0) VCF_LBT_DEC(0);
-        else if (cls == 1) VCF_LBT_DEC(1);
-        else VCF_LBT_DEC(2);
-#undef VCF_LBT_DEC
-        rc = hip_check(hipGetLastError(), "lbt_decode_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    return for_frame_chunks(n_frames, "lbt_decode_kernel launch", [&](int64_t f0, unsigned nf) {
+        with_lds_class(p.cls, [&](auto lds) {
+            hipLaunchKernelGGL((lbt_decode_kernel<decltype(lds)::value>), dim3((unsigned)p.tiles, nf), dim3(kTileThreads),
+                               0, (hipStream_t)stream, k_dev + f0 * g.k_stride, rgb_dev + f0 * g.rgb_stride,
+                               wd_dev + f0 * DD, mean_dev + f0, g, (int)Q, sub, pq);
+        });
+    });
 }
 
 }  // extern "C"

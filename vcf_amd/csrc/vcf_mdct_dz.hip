@@ -551,8 +551,8 @@ int vcf_mdct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int3
     if ((rc = device_tables(g.N, tab)) != VCF_OK) return rc;
     const float scale = scale_factor(g.N);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1, perc = (flags & VCF_DCT_PERCEPTUAL) ? 1 : 0;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid(g.tiles_x * g.tiles_y, (unsigned)std::min<int64_t>(65535, n_frames - f0));
+    return for_frame_chunks(n_frames, "mdct_encode_kernel launch", [&](int64_t f0, unsigned nf) {
+        const dim3 grid(g.tiles_x * g.tiles_y, nf);
         const uint8_t *in = rgb_dev + f0 * g.rgb_stride;
         uint8_t *out = k_dev + f0 * g.k_stride;
 #define VCF_MDCT_ENC(C)                                                                                          \
@@ -562,10 +562,7 @@ int vcf_mdct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int3
         else if (cls == 1) VCF_MDCT_ENC(1);
         else VCF_MDCT_ENC(2);
 #undef VCF_MDCT_ENC
-        rc = hip_check(hipGetLastError(), "mdct_encode_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    });
 }
 
 int vcf_mdct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
@@ -582,8 +579,8 @@ int vcf_mdct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_
     if ((rc = device_tables(g.N, tab)) != VCF_OK) return rc;
     const float scale = scale_factor(g.N);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1, pow2 = (g.N & (g.N - 1)) == 0 ? 1 : 0;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 65535) {
-        const dim3 grid(g.tiles_x * g.tiles_y, (unsigned)std::min<int64_t>(65535, n_frames - f0));
+    return for_frame_chunks(n_frames, "mdct_decode_kernel launch", [&](int64_t f0, unsigned nf) {
+        const dim3 grid(g.tiles_x * g.tiles_y, nf);
         const uint8_t *in = k_dev + f0 * g.k_stride;
         uint8_t *out = rgb_dev + f0 * g.rgb_stride;
 #define VCF_MDCT_DEC(C, PC)                                                                                      \
@@ -599,10 +596,7 @@ int vcf_mdct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_
             else VCF_MDCT_DEC(2, false);
         }
 #undef VCF_MDCT_DEC
-        rc = hip_check(hipGetLastError(), "mdct_decode_kernel launch");
-        if (rc != VCF_OK) return rc;
-    }
-    return VCF_OK;
+    });
 }
 
 }  // extern "C"
