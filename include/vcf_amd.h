@@ -333,6 +333,25 @@ int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
 int vcf_dwt_dz_decode(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                       int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream);
 
+/* What vcf_dwt_dz_encode / _decode launch for a call of these arguments, from
+ * the code the launches themselves consult (host only, no device work).  For
+ * level l = 1..levels, enc_kind[l-1] / dec_kind[l-1] is the kernel family
+ * below (a kernel that covers two levels is reported on both), and enc_ct[l-1]
+ * / dec_ct[l-1] the compile-time tap set of the instantiation: 0 = taps read
+ * at run time, 1 = bior4.4's, 2 = db5's.  n_frames is validated as the calls
+ * validate it; the families do not depend on it. */
+#define VCF_DWT_ENC_SEPARABLE 0        /* column pass + row pass, any filter length */
+#define VCF_DWT_ENC_FUSED 1            /* one tile kernel per level, F <= 18 */
+#define VCF_DWT_ENC_STRIP 2            /* sliding-window strips, F <= 10, levels between first and last */
+#define VCF_DWT_ENC_BAND12 3           /* levels 1 + 2 in one launch */
+#define VCF_DWT_DEC_SEPARABLE 0
+#define VCF_DWT_DEC_SEPARABLE_SHORT 1  /* separable, this level's subbands shorter than F/2 (pywt's short-input branch) */
+#define VCF_DWT_DEC_FUSED 2
+#define VCF_DWT_DEC_LINE 3             /* line-based inverse level */
+#define VCF_DWT_DEC_BAND21 4           /* inverse levels 2 + 1 in one launch */
+int vcf_dwt_plan(int32_t H, int32_t W, int32_t wavelet, int32_t levels, int64_t n_frames, int32_t *enc_kind,
+                 int32_t *enc_ct, int32_t *dec_kind, int32_t *dec_ct);
+
 /* Opt-in lifting form of the two calls above for bior4.4 (CDF 9/7) only
  * (VCF_ERR_INVALID for other wavelets): same arguments, buffers, layout and
  * workspace, four lifting steps per axis in place of pywt's convolution.

@@ -1394,6 +1394,32 @@ unsigned zero_mask(const double *t, int F)
 // reconstruction lo / hi
 constexpr unsigned kB44DecLo = 0x001u, kB44DecHi = 0x301u, kB44RecLo = 0x301u, kB44RecHi = 0x001u;
 
+// the compile-time tap set (ct_dec / ct_rec: 1 bior4.4, 2 db5) that a 10-tap wavelet's decomposition /
+// reconstruction filters equal bit for bit; 0: none, the kernels read their taps at run time
+int ct_dec_id(const WaveletDef &wd)
+{
+    if (wd.len != 10) return 0;
+    const bool b44 = zero_mask(wd.dec_lo, 10) == kB44DecLo && zero_mask(wd.dec_hi, 10) == kB44DecHi;
+    const int id = b44 ? 1 : 2;
+    for (int m = 0; m < 10; ++m) {
+        const double l = ct_dec(id, false, m), h = ct_dec(id, true, m);
+        if (std::memcmp(&l, &wd.dec_lo[m], 8) || std::memcmp(&h, &wd.dec_hi[m], 8)) return 0;
+    }
+    return id;
+}
+
+int ct_rec_id(const WaveletDef &wd)
+{
+    if (wd.len != 10) return 0;
+    const bool b44 = zero_mask(wd.rec_lo, 10) == kB44RecLo && zero_mask(wd.rec_hi, 10) == kB44RecHi;
+    const int id = b44 ? 1 : 2;
+    for (int m = 0; m < 10; ++m) {
+        const double l = ct_rec(id, false, m), h = ct_rec(id, true, m);
+        if (std::memcmp(&l, &wd.rec_lo[m], 8) || std::memcmp(&h, &wd.rec_hi[m], 8)) return 0;
+    }
+    return id;
+}
+
 template <int F, unsigned ZLO, unsigned ZHI>
 void launch_fwd_kernel(const LevelArgs &a, const Taps<F> &tp, const dim3 &grid, bool first, bool last)
 {
@@ -1402,12 +1428,7 @@ void launch_fwd_kernel(const LevelArgs &a, const Taps<F> &tp, const dim3 &grid, 
     if constexpr (F == 10) {   // bior4.4 / db5: compile-time taps, sums started by their first product
         constexpr int id = ZLO != 0 ? 1 : 2;
         constexpr int stg = id == 2 ? 1 : 0;
-        bool ct = true;
-        for (int m = 0; m < F; ++m) {
-            const double l = ct_dec(id, false, m), h = ct_dec(id, true, m);
-            ct = ct && std::memcmp(&l, &tp.lo[m], 8) == 0 && std::memcmp(&h, &tp.hi[m], 8) == 0;
-        }
-        if (ct)
+        if (ct_dec_id(*a.wd) == id)
             kern = first ? (last ? dwt_level_kernel<F, true, true, ZLO, ZHI, id, stg, true>
                                  : dwt_level_kernel<F, true, false, ZLO, ZHI, id, stg, true>)
                          : (last ? dwt_level_kernel<F, false, true, ZLO, ZHI, id, 0, true>
@@ -1464,17 +1485,11 @@ void launch_strip_level(const LevelArgs &a, bool first, bool last)
         const bool qp2 = (a.Q & (a.Q - 1)) == 0;
         StripKern<F> kern = qp2 ? strip_kern<F, 0u, 0u, 0, true>(first, last) : strip_kern<F, 0u, 0u, 0, false>(first, last);
         if constexpr (F == 10) {   // bior4.4 (zero taps skipped) / db5: compile-time taps
-            const bool b44 = zero_mask(a.wd->dec_lo, F) == kB44DecLo && zero_mask(a.wd->dec_hi, F) == kB44DecHi;
-            const int id = b44 ? 1 : 2;
-            bool ct = true;
-            for (int m = 0; ct && m < F; ++m) {
-                const double l = ct_dec(id, false, m), h = ct_dec(id, true, m);
-                ct = std::memcmp(&l, &tp.lo[m], 8) == 0 && std::memcmp(&h, &tp.hi[m], 8) == 0;
-            }
-            if (ct && b44)
+            const int id = ct_dec_id(*a.wd);
+            if (id == 1)
                 kern = qp2 ? strip_kern<F, kB44DecLo, kB44DecHi, 1, true>(first, last)
                            : strip_kern<F, kB44DecLo, kB44DecHi, 1, false>(first, last);
-            else if (ct)
+            else if (id == 2)
                 kern = qp2 ? strip_kern<F, 0u, 0u, 2, true>(first, last) : strip_kern<F, 0u, 0u, 2, false>(first, last);
         }
         hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(192), 0, a.s, a.rgb, a.rgb_stride, a.in,
@@ -1493,12 +1508,7 @@ void launch_inv_kernel(const LevelArgs &a, const Taps<F> &tp, dim3 grid, bool fr
                     : (to_rgb ? idwt_level_kernel<F, false, true, ZLO, ZHI> : idwt_level_kernel<F, false, false, ZLO, ZHI>);
     if constexpr (F == 10) {   // bior4.4 / db5: compile-time taps
         constexpr int id = ZLO != 0 ? 1 : 2;
-        bool ct = true;
-        for (int m = 0; m < F; ++m) {
-            const double l = ct_rec(id, false, m), h = ct_rec(id, true, m);
-            ct = ct && std::memcmp(&l, &tp.lo[m], 8) == 0 && std::memcmp(&h, &tp.hi[m], 8) == 0;
-        }
-        if (ct)
+        if (ct_rec_id(*a.wd) == id)
             kern = from_packed ? (to_rgb ? idwt_level_kernel<F, true, true, ZLO, ZHI, id>
                                          : idwt_level_kernel<F, true, false, ZLO, ZHI, id>)
                                : (to_rgb ? idwt_level_kernel<F, false, true, ZLO, ZHI, id>
@@ -1527,13 +1537,8 @@ void launch_inv_level(const LevelArgs &a, bool from_packed, bool to_rgb, uint8_t
 bool band12_ok(const DwtGeom &g, const WaveletDef &wd, int &id)
 {
     if (g.F != 10 || g.levels < 2 || g.H % 4 || g.W % 4 || g.H < 64 || g.W < 512) return false;
-    const bool b44 = zero_mask(wd.dec_lo, 10) == kB44DecLo && zero_mask(wd.dec_hi, 10) == kB44DecHi;
-    id = b44 ? 1 : 2;
-    for (int m = 0; m < 10; ++m) {
-        const double l = ct_dec(id, false, m), h = ct_dec(id, true, m);
-        if (std::memcmp(&l, &wd.dec_lo[m], 8) || std::memcmp(&h, &wd.dec_hi[m], 8)) return false;
-    }
-    return true;
+    id = ct_dec_id(wd);
+    return id != 0;
 }
 
 template <unsigned ZL, unsigned ZH, int CT>
@@ -1576,13 +1581,8 @@ void launch_band12(int id, const DwtGeom &g, const uint8_t *rgb, long long n_fra
 bool line_ok(const WaveletDef &wd, int h, int w, int &id)
 {
     if (wd.len != 10 || h < 5 || w < 5) return false;
-    const bool b44 = zero_mask(wd.rec_lo, 10) == kB44RecLo && zero_mask(wd.rec_hi, 10) == kB44RecHi;
-    id = b44 ? 1 : 2;
-    for (int m = 0; m < 10; ++m) {
-        const double l = ct_rec(id, false, m), hv = ct_rec(id, true, m);
-        if (std::memcmp(&l, &wd.rec_lo[m], 8) || std::memcmp(&hv, &wd.rec_hi[m], 8)) return false;
-    }
-    return true;
+    id = ct_rec_id(wd);
+    return id != 0;
 }
 
 template <bool FP, bool RGB, unsigned ZL, unsigned ZH, int CT>
@@ -1806,9 +1806,84 @@ int vcf_dwt_layout(int32_t H, int32_t W, int32_t levels, int32_t *sub_h, int32_t
 // on C3, ABBA); filters longer than kMaxFastF on the separable kernels alone.
 constexpr long long kSepArea = 40000;
 
+// The kernel family of every level of a call (VCF_DWT_ENC_* / VCF_DWT_DEC_*, include/vcf_amd.h)
+// and its compile-time tap set (0 = run-time taps): the rules of the comments above
+// encode_chain and decode_chain_fast, decided here alone.  The chains launch what the plan
+// says; vcf_dwt_plan reports it.
+struct DwtPlan {
+    int enc[kMaxLevels + 1], enc_ct[kMaxLevels + 1];   // [l], l = 1 .. levels
+    int dec[kMaxLevels + 1], dec_ct[kMaxLevels + 1];
+    bool dec_fast;                                     // decode_chain_fast runs the decode, else the separable chain
+};
+
+static void dwt_plan(const DwtGeom &g, const WaveletDef &wd, const DwtSchedule &sc, DwtPlan &p)
+{
+    const int F = g.F, levels = g.levels;
+    const bool fused = fast_filter(F);
+    int l = 1, id = 0;
+    if (fused && band12_ok(g, wd, id)) {
+        p.enc[1] = p.enc[2] = VCF_DWT_ENC_BAND12;
+        p.enc_ct[1] = p.enc_ct[2] = id;
+        l = 3;
+    }
+    for (; l <= levels; ++l) {
+        if (!fused || (l > 1 && (long long)g.hs[l - 1] * g.ws[l - 1] <= kSepArea)) {
+            p.enc[l] = VCF_DWT_ENC_SEPARABLE;
+            p.enc_ct[l] = 0;
+            continue;
+        }
+        // strips need planes of at least 2F rows and columns (their row wrap)
+        const bool strip = F <= kMaxStripF && g.hs[l - 1] >= 2 * F && g.ws[l - 1] >= 2 * F && l > 1 && l < levels;
+        p.enc[l] = strip ? VCF_DWT_ENC_STRIP : VCF_DWT_ENC_FUSED;
+        p.enc_ct[l] = ct_dec_id(wd);
+    }
+    const bool short_lines = g.hs[levels] < F / 2 || g.ws[levels] < F / 2;
+    p.dec_fast = fused && !short_lines;
+    int id21 = 0;
+    const bool b21 = p.dec_fast && sc.band21 && band21_ok(g, wd, id21);
+    for (int r = levels; r >= 1; --r) {
+        const int h = g.hs[r], w = g.ws[r];
+        p.dec_ct[r] = 0;
+        if (!p.dec_fast) {
+            p.dec[r] = h < F / 2 || w < F / 2 ? VCF_DWT_DEC_SEPARABLE_SHORT : VCF_DWT_DEC_SEPARABLE;
+        } else if (b21 && r <= 2) {
+            p.dec[r] = VCF_DWT_DEC_BAND21;
+            p.dec_ct[r] = id21;
+        } else if (line_ok(wd, h, w, id)) {
+            p.dec[r] = VCF_DWT_DEC_LINE;
+            p.dec_ct[r] = id;
+        } else {
+            p.dec[r] = VCF_DWT_DEC_FUSED;
+            p.dec_ct[r] = ct_rec_id(wd);
+        }
+    }
+}
+
+#ifndef VCF_DWT_SCHED_BUILD
+int vcf_dwt_plan(int32_t H, int32_t W, int32_t wavelet, int32_t levels, int64_t n_frames, int32_t *enc_kind,
+                 int32_t *enc_ct, int32_t *dec_kind, int32_t *dec_ct)
+{
+    if (!enc_kind || !enc_ct || !dec_kind || !dec_ct) return set_error(VCF_ERR_INVALID, "null pointer");
+    const int rc = check_dwt(nullptr, nullptr, 0, H, W, wavelet, levels, 1, false);
+    if (rc != VCF_OK) return rc;
+    if (n_frames < 0 || n_frames * 3 > 65535) return set_error(VCF_ERR_INVALID, "0 to 21845 frames per call");
+    DwtGeom g;
+    dwt_geom(H, W, levels, kWavelets[wavelet].len, g);
+    DwtPlan p;
+    dwt_plan(g, kWavelets[wavelet], DwtSchedule{}, p);
+    for (int l = 1; l <= levels; ++l) {
+        enc_kind[l - 1] = p.enc[l];
+        enc_ct[l - 1] = p.enc_ct[l];
+        dec_kind[l - 1] = p.dec[l];
+        dec_ct[l - 1] = p.dec_ct[l];
+    }
+    return VCF_OK;
+}
+#endif
+
 static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                         int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, hipStream_t s,
-                        const PipeHook *hook, long long rule_frames, const DwtSchedule &sc)
+                        const PipeHook *hook, long long rule_frames, const DwtSchedule &sc, const DwtPlan &plan)
 {
     int rc = VCF_OK;
     Filters flt;
@@ -1821,7 +1896,6 @@ static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int
     double *const A = pl.A, *const D = pl.D, *const LL0 = pl.P0, *const LL1 = pl.P1;
     const unsigned planes = (unsigned)(n_frames * 3);
     const double *in = nullptr;
-    const bool fused = fast_filter(F);
     // one level on the separable kernels (column pass, then the row pass into the subbands / LL)
     auto sep_level = [&](int l) {
         const int h = g.hs[l - 1], w = g.ws[l - 1], hh = g.hs[l], hw = g.ws[l];
@@ -1842,11 +1916,10 @@ static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int
                                g.sb_off[l][1], g.sb_off[l][2], hh, w, hw, F, Q, flt);
     };
     int l_start = 1;
-    int band_id = 0;
-    if (fused && band12_ok(g, kWavelets[wavelet], band_id)) {
+    if (plan.enc[1] == VCF_DWT_ENC_BAND12) {
         // levels 1 and 2 in one launch: LL1 never leaves the chip; LL2 lands where level 2's would
         if ((rc = hook_wait(hook, s)) != VCF_OK) return rc;
-        launch_band12(band_id, g, rgb_dev, n_frames, LL1, ws_stride, packed_dev, Q, s, rule_frames, sc);
+        launch_band12(plan.enc_ct[1], g, rgb_dev, n_frames, LL1, ws_stride, packed_dev, Q, s, rule_frames, sc);
         if ((rc = hip_check(hipGetLastError(), "dwt_band12_kernel launch")) != VCF_OK) return rc;
         if ((rc = hook_rec(hook, s)) != VCF_OK) return rc;
         in = LL1;
@@ -1855,15 +1928,13 @@ static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int
     for (int l = l_start; l <= levels; ++l) {
         double *LLout = (l & 1) ? LL0 : LL1;
         if (l == 1 && (rc = hook_wait(hook, s)) != VCF_OK) return rc;
-        if (!fused || (l > 1 && (long long)g.hs[l - 1] * g.ws[l - 1] <= kSepArea)) {
+        if (plan.enc[l] == VCF_DWT_ENC_SEPARABLE) {
             sep_level(l);
         } else {
             const LevelArgs a{rgb_dev, (long long)H * W * 3, in, ws_stride, LLout, packed_dev, g.packed_bytes, g.ll_off,
                               g.sb_off[l][0], g.sb_off[l][1], g.sb_off[l][2], g.hs[l - 1], g.ws[l - 1], g.hs[l],
                               g.ws[l], Q, 0, (unsigned)n_frames, flt, &kWavelets[wavelet], s};
-            // strips need planes of at least 2F rows and columns (their row wrap)
-            const bool strip = F <= kMaxStripF && g.hs[l - 1] >= 2 * F && g.ws[l - 1] >= 2 * F && l > 1 && l < levels;
-            if (strip) strip_level(F, a, false, false);
+            if (plan.enc[l] == VCF_DWT_ENC_STRIP) strip_level(F, a, false, false);
             else fwd_level(F, a, l == 1, l == levels);
         }
         in = LLout;
@@ -1884,21 +1955,23 @@ static int dwt_encode(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_f
     hipStream_t s = (hipStream_t)stream;
     DwtGeom g;
     dwt_geom(H, W, levels, kWavelets[wavelet].len, g);
-    int id = 0;
+    DwtPlan plan;
+    dwt_plan(g, kWavelets[wavelet], sc, plan);
     // the frame pipeline pays only for the level-by-level chain: with the fused
     // level-1+2 band kernel one launch fills the chip (C3: 0.594 ms on one
     // stream vs 0.635 ms pipelined, ABBA)
-    const bool band = fast_filter(g.F) && band12_ok(g, kWavelets[wavelet], id);
+    const bool band = plan.enc[1] == VCF_DWT_ENC_BAND12;
     // (A/B: sc.enc_pipe 0 / 1; with the band kernel the chunks keep the call's band cut)
     const bool pipe = (sc.enc_pipe < 0 ? !band : sc.enc_pipe != 0) && fast_filter(g.F) && pipeline_default(n_frames, H, W);
     if (pipe) {
         const long long fpx = (long long)H * W * 3, wsf = 3 * plane_doubles(g);
         return run_pipelined(n_frames, kEncodePipe, s, [&](long long f0, long long n, hipStream_t cs, const PipeHook *hook) {
             return encode_chain(rgb_dev + f0 * fpx, n, H, W, wavelet, levels, Q, packed_dev + f0 * g.packed_bytes,
-                                (double *)workspace_dev + f0 * wsf, cs, hook, n_frames, sc);
+                                (double *)workspace_dev + f0 * wsf, cs, hook, n_frames, sc, plan);
         });
     }
-    return encode_chain(rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev, s, nullptr, n_frames, sc);
+    return encode_chain(rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev, s, nullptr, n_frames, sc,
+                        plan);
 }
 
 // one stream's level chain of the decode: coarsest level first; the line
@@ -1910,7 +1983,7 @@ static int dwt_encode(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_f
 // calls it per chunk); rule_frames: the call's frames, for the band cut of levels 2 + 1
 static int decode_chain_fast(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                              int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, hipStream_t s,
-                             long long rule_frames, const DwtSchedule &sc)
+                             long long rule_frames, const DwtSchedule &sc, const DwtPlan &plan)
 {
     int rc = VCF_OK;
     Filters flt;
@@ -1922,11 +1995,9 @@ static int decode_chain_fast(const uint8_t *packed_dev, int64_t n_frames, int32_
     const DwtPlanes pl = dwt_planes(g, workspace_dev);
     const double *prev = nullptr;
     int lda = 0;
-    int id21 = 0;
-    const bool b21 = sc.band21 && band21_ok(g, kWavelets[wavelet], id21);
     for (int r = levels; r >= 1; --r) {
-        if (b21 && r == 2) {   // levels 2 and 1 in one launch, LL1 on chip
-            launch_band21(id21, g, packed_dev, n_frames, prev, ws_stride, lda, rgb_dev, Q, s, rule_frames, sc);
+        if (plan.dec[r] == VCF_DWT_DEC_BAND21) {   // levels 2 and 1 in one launch, LL1 on chip
+            launch_band21(plan.dec_ct[r], g, packed_dev, n_frames, prev, ws_stride, lda, rgb_dev, Q, s, rule_frames, sc);
             return hip_check(hipGetLastError(), "idwt_band21_kernel launch");
         }
         const int h = g.hs[r], w = g.ws[r];
@@ -1935,8 +2006,7 @@ static int decode_chain_fast(const uint8_t *packed_dev, int64_t n_frames, int32_
         const LevelArgs a{nullptr, 0, prev, ws_stride, out, const_cast<uint8_t *>(packed_dev), g.packed_bytes,
                           g.ll_off, g.sb_off[r][0], g.sb_off[r][1], g.sb_off[r][2], h, w, oh, ow, Q, lda,
                           (unsigned)n_frames, flt, &kWavelets[wavelet], s};
-        int id = 0;
-        if (line_ok(kWavelets[wavelet], h, w, id)) launch_line(id, a, r == levels, r == 1, rgb_dev, sc);
+        if (plan.dec[r] == VCF_DWT_DEC_LINE) launch_line(plan.dec_ct[r], a, r == levels, r == 1, rgb_dev, sc);
         else inv_level(F, a, r == levels, r == 1, rgb_dev);
         prev = out;
         lda = ow;
@@ -1972,16 +2042,18 @@ static int dwt_decode(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t 
     const unsigned planes = (unsigned)(n_frames * 3);
     const double *prev = nullptr;
     int lda = 0;
-    const bool short_lines = g.hs[levels] < F / 2 || g.ws[levels] < F / 2;
-    if (fast_filter(F) && !short_lines) {
+    DwtPlan plan;
+    dwt_plan(g, kWavelets[wavelet], sc, plan);
+    if (plan.dec_fast) {
         if (sc.dec_pipe > 0 && pipeline_default(n_frames, H, W)) {
             const long long fpx = (long long)H * W * 3, wsf = 3 * pd;
             return run_pipelined(n_frames, kDecodePipe, s, [&](long long f0, long long n, hipStream_t cs, const PipeHook *) {
                 return decode_chain_fast(packed_dev + f0 * g.packed_bytes, n, H, W, wavelet, levels, Q,
-                                         rgb_dev + f0 * fpx, (double *)workspace_dev + f0 * wsf, cs, n_frames, sc);
+                                         rgb_dev + f0 * fpx, (double *)workspace_dev + f0 * wsf, cs, n_frames, sc, plan);
             });
         }
-        return decode_chain_fast(packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev, s, n_frames, sc);
+        return decode_chain_fast(packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev, s, n_frames, sc,
+                                 plan);
     }
     for (int r = levels; r >= 1; --r) {
         const int h = g.hs[r], w = g.ws[r];

@@ -32,6 +32,20 @@ def layout(H: int, W: int, levels: int):
     return list(zip(hs[:], ws[:])), pb.value, wb.value
 
 
+ENC_KINDS = ("separable", "fused", "strip", "band12")                           # VCF_DWT_ENC_*
+DEC_KINDS = ("separable", "separable_short", "fused", "line", "band21")       # VCF_DWT_DEC_*
+
+
+def plan(H: int, W: int, wavelet: str, levels: int, n_frames: int = 1):
+    """What encode() and decode() launch under the default schedule, from the library's own
+    dispatch (vcf_dwt_plan; host only): (encode, decode), each a list over levels 1..levels of
+    (kernel family name from ENC_KINDS / DEC_KINDS, compile-time tap set: 0 run-time taps,
+    1 bior4.4's, 2 db5's)."""
+    v = [(ctypes.c_int32 * levels)() for _ in range(4)]
+    L.call("vcf_dwt_plan", H, W, wavelet_index(wavelet), levels, n_frames, *v)
+    return ([(ENC_KINDS[k], c) for k, c in zip(v[0], v[1])], [(DEC_KINDS[k], c) for k, c in zip(v[2], v[3])])
+
+
 def subband_names(levels: int):
     """File order of write_decom_fn (2D-DWT.py:162-200)."""
     return [f"LL_{levels}"] + [f"{s}_{r}" for r in range(levels, 0, -1) for s in ("LH", "HL", "HH")]
