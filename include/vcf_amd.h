@@ -869,6 +869,34 @@ int vcf_vq_fit(const uint8_t *img_dev, int32_t H, int32_t W, int32_t C, int32_t 
 int vcf_vq_decode(const uint16_t *labels_dev, int32_t Hl, int32_t Wl, int32_t C, int32_t block_size,
                   const double *centroids_dev, int32_t K, uint8_t *img_dev, int32_t *bad_dev, void *stream);
 
+/* ---- distortion between two sets of u8 frames (src/RDE.py) -----------------------
+ *
+ * What RDE.py's calculate_rmse needs, as exact integers.  a_dev and b_dev hold
+ * n_frames contiguous frames of H x W x C uint8 samples each (channel fastest),
+ * 1 <= C <= 4; out_dev receives n_frames x C records, record f * C + c for
+ * frame f and channel c, with d = |a - b| over the H * W samples of that
+ * channel:
+ *     sse = sum d * d,   sad = sum d,   max_abs = max d,   pad = 0.
+ * Integer arithmetic throughout: 32-bit partial sums are widened to 64 bits long
+ * before they could overflow, and the 64-bit sums and the maximum depend on no
+ * launch geometry and on no order.  The call zeroes the records itself (on
+ * `stream`, before the kernel), so a repeated call into the same out_dev gives
+ * the same records.  out_dev is 8-byte aligned; the frames need no alignment
+ * (frames whose addresses differ by a multiple of 16 bytes, as two hipMalloc'd
+ * sets always do, run at full speed; others are read bytewise).  C outside
+ * 1..4, a negative size, a null or misaligned pointer: VCF_ERR_INVALID before
+ * any device work.  n_frames = 0 or H * W = 0: VCF_OK, nothing is enqueued and
+ * out_dev is left untouched.  Otherwise the work is enqueued on `stream`.
+ * RMSE = sqrt((double)(sum of sse over c) / (H * W * C)) (vcf_amd/distortion.py). */
+typedef struct vcf_distortion_record {
+    uint64_t sse;
+    uint64_t sad;
+    uint32_t max_abs;
+    uint32_t pad;
+} vcf_distortion_record;
+int vcf_distortion_u8(const uint8_t *a_dev, const uint8_t *b_dev, int64_t n_frames, int32_t H, int32_t W, int32_t C,
+                      vcf_distortion_record *out_dev, void *stream);
+
 /* ---- cross-rank exchange on RCCL over xGMI -------------------
  * Frames shard across one process per GPU with no collective on the data
  * path; the one exchange step of the III / IPP drivers is after coding: an

@@ -445,6 +445,45 @@ def cbahc_parser(description: str = "\n# Huffman adaptativo\n"):
     return p
 
 
+RDE_CODESTREAM = "/tmp/encoded*"         # RDE.py:80
+
+
+def rde_parser(description: str = "Compute the rate/distortion efficiency (J=R+D)."):
+    """`python RDE.py ...` (RDE.py:70-86: a plain ArgumentParser, no subcommands), plus -N, which the
+    reference does not have."""
+    p = argparse.ArgumentParser(description=description)
+    p.add_argument("-o", "--original", type=str, help="Original image (default: %(default)s)", default=ORIGINAL)
+    p.add_argument("-c", "--codestream", type=str, help="Codestream (default: %(default)s)", default=RDE_CODESTREAM)
+    p.add_argument("-d", "--decoded", type=str, help="Decoded image (default: %(default)s)", default=DECODED)
+    p.add_argument("-N", "--number_of_frames", type=int, default=None,
+                   help="Not in the reference: evaluate this many frames; -o, -c and -d are then printf patterns "
+                        "of the frame number, such as /tmp/original_%%04d.png, /tmp/encoded_%%04d and "
+                        "/tmp/decoded_%%04d.png (default: one image)")
+    return p
+
+
+def rd_curve_parser(description: str = "Rate-distortion curve of the default chain (2D-DCT, YCoCg, deadzone, "
+                                       "TIFF) with the frames resident on the GPU. This program has no "
+                                       "counterpart in the reference: it replaces a loop of 2D-DCT.py encode, "
+                                       "2D-DCT.py decode and RDE.py over -q values."):
+    """`python RD-curve.py ...`: -B, -p and -x as 2D-DCT.py names them."""
+    p = argparse.ArgumentParser(description=description)
+    p.add_argument("-o", "--original", type=str, default=ORIGINAL,
+                   help="Input image; with -N a printf pattern of the frame number; or an .npy file holding "
+                        "N x H x W x 3 uint8 frames (default: %(default)s)")
+    p.add_argument("-N", "--number_of_frames", type=int, default=None, help="Number of frames of the pattern -o")
+    p.add_argument("-q", "--QSS", type=str, default="8,16,32,64",
+                   help="Quantization step sizes, comma separated (default: %(default)s)")
+    p.add_argument("-B", "--block_size_DCT", type=int, help=f"Block size (default: {DEFAULT_BLOCK_SIZE})",
+                   default=DEFAULT_BLOCK_SIZE)
+    p.add_argument("-p", "--perceptual_quantization", action="store_true",
+                   help="Use perceptual quantization (default: \"False\")", default=False)
+    p.add_argument("-x", "--disable_subbands", action="store_true",
+                   help="Disable the coefficients reordering in subbands (default: \"False\")", default=False)
+    p.add_argument("--json", action="store_true", help="Print one JSON line with the per-frame values of every Q")
+    return p
+
+
 def parse(parser, argv=None):
     """parser.parse_known_args()[0] as main.py:9 does."""
     return parser.parse_known_args(argv)[0]

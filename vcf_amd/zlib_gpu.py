@@ -215,6 +215,28 @@ def tiff_frames_device(src: DeviceBuffer, n_frames: int, shape, dtype=np.uint8, 
     return [container(shape, dt, s) for s in strips]
 
 
+def tiff_sizes_device(src: DeviceBuffer, n_frames: int, shape, dtype=np.uint8, offset: int = 0,
+                      stream: Stream | None = None) -> np.ndarray:
+    """len() of each file tiff_frames_device would return (int64 per frame), from the strips'
+    compressed sizes alone: the strips are deflated where they are and only their sizes come
+    back; the bytes in front of the strip data do not depend on them (codec/tiff.py)."""
+    from .codec.tiff import container_prefix, strip_layout
+    dt = np.dtype(dtype)
+    if dt not in (np.uint8, np.uint16):
+        raise ValueError(f"current type = {dt}")   # TIFF.py:27
+    shape = tuple(int(s) for s in shape)
+    frame_bytes = int(np.prod(shape)) * dt.itemsize
+    _, spf, strip_bytes = strip_layout(shape if len(shape) == 3 else shape + (1,), dt.itemsize)
+    prefix = len(container_prefix(shape, dt, [0] * spf))
+    d = deflater()
+    with d._lock:
+        d.launch(src, n_frames, frame_bytes, strip_bytes, LEVEL, offset, stream)
+        if d.total == 0:
+            return np.full(int(n_frames), prefix, np.int64)
+        sz = d.sizes().reshape(int(n_frames), d.spf)
+    return prefix + sz.sum(axis=1, dtype=np.int64)
+
+
 class StripInflater:
     """zlib.decompress of a batch of strips on the GPU (vcf_inflate_strips), the
     decode side of TIFF.py:33-39: the compressed strips go up in one copy, the
