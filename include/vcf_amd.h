@@ -897,6 +897,45 @@ typedef struct vcf_distortion_record {
 int vcf_distortion_u8(const uint8_t *a_dev, const uint8_t *b_dev, int64_t n_frames, int32_t H, int32_t W, int32_t C,
                       vcf_distortion_record *out_dev, void *stream);
 
+/* ---- SSIM between two sets of u8 frames, exact by construction ---
+ *
+ * a_dev and b_dev hold n_frames contiguous frames of H x W x C uint8 samples each
+ * (channel fastest), C = 1 or 3, H and W at least 11; out_dev receives n_frames x C
+ * records, record f * C + c for frame f and channel c.  The window is Wang et
+ * al.'s 11 x 11 Gaussian (sigma 1.5), separable, each axis scaled to sum 256 and
+ * rounded: w = {0, 2, 9, 28, 55, 68, 55, 28, 9, 2, 0} (the outer taps round to 0:
+ * the support is 9 x 9 inside the 11 x 11 footprint), 2-D weight sum S = 2^16.
+ * Only the (H - 10) * (W - 10) windows that lie wholly inside the frame count.
+ * Per window, with x from a and y from b, as exact integers:
+ *     A = sum w_i w_j x,  B = sum w_i w_j y,
+ *     XX = sum w_i w_j x^2,  YY = sum w_i w_j y^2,  XY = sum w_i w_j x y,
+ *     f1 = 2 A B + C1,            f2 = 2 (S XY - A B) + C2,
+ *     f3 = A^2 + B^2 + C1,        f4 = S XX - A^2 + S YY - B^2 + C2,
+ * C1 = 27928024842 = round(6.5025 * 2^32), C2 = 251352223580 = round(58.5225 * 2^32).
+ * Every factor is below 2^50 in magnitude, so its conversion to double is exact;
+ *     q = ((double)f1 * (double)f2) / ((double)f3 * (double)f4)
+ * is two IEEE multiplications and one IEEE division (round to nearest), and
+ *     k = (int64) rint(q * 2^30)          (ties to even; k can be negative).
+ * sum_k and min_k are the sum and the minimum of k over the windows; windows is
+ * their number.  SSIM = sum_k / (windows * 2^30), divided on the host.  Integer
+ * sums and minima depend on no launch geometry and on no order.  The call sets
+ * the records itself (on `stream`, before the kernel).  out_dev is 8-byte
+ * aligned; the frames need no alignment.  A null pointer, n_frames < 1, C other
+ * than 1 or 3, H < 11 or W < 11, a misaligned out_dev: VCF_ERR_INVALID before any
+ * device work, and nothing is written.  Otherwise the work is enqueued on
+ * `stream`. */
+#define VCF_SSIM_WINDOW 11
+#define VCF_SSIM_ONE (1 << 30)
+typedef struct vcf_ssim_record {
+    int64_t sum_k;
+    uint64_t windows;
+    int64_t min_k;
+} vcf_ssim_record;
+int vcf_ssim_u8(const uint8_t *a_dev, const uint8_t *b_dev, int64_t n_frames, int32_t H, int32_t W, int32_t C,
+                vcf_ssim_record *out_dev, void *stream);
+/* The edge, in windows, of the square tile one workgroup of vcf_ssim_u8 takes (for tests and benchmarks). */
+int vcf_ssim_tile(void);
+
 /* ---- cross-rank exchange on RCCL over xGMI -------------------
  * Frames shard across one process per GPU with no collective on the data
  * path; the one exchange step of the III / IPP drivers is after coding: an

@@ -128,6 +128,8 @@ SIGNATURES = {
     "vcf_vq_fit": [_P, _I32, _I32, _I32, _I32, _I32, ctypes.c_uint64, _I32, ctypes.c_double, _P, _P, _P, _P, _P],
     "vcf_vq_decode": [_P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P],
     "vcf_distortion_u8": [_P, _P, _I64, _I32, _I32, _I32, _P, _P],
+    "vcf_ssim_u8": [_P, _P, _I64, _I32, _I32, _I32, _P, _P],
+    "vcf_ssim_tile": [],
     "vcf_wavelet_index": [ctypes.c_char_p, _PI32],
     "vcf_dwt_layout": [_I32, _I32, _I32, _PI32, _PI32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
     "vcf_dwt_plan": [_I32, _I32, _I32, _I32, _I64, _PI32, _PI32, _PI32, _PI32],

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for `python RDE.py [-o original] [-c codestream] [-d decoded]` (src/RDE.py): sizes, bits
-per pixel, RMSE and J = R + D, the distortion measured on the GPU; -N evaluates a frame sequence."""
+per pixel, RMSE and J = R + D, the distortion measured on the GPU; -N evaluates a frame sequence, --ssim
+adds one `RDE: SSIM: x.xxxx` line."""
 import os
 import sys
 

@@ -459,6 +459,9 @@ def rde_parser(description: str = "Compute the rate/distortion efficiency (J=R+D
                    help="Not in the reference: evaluate this many frames; -o, -c and -d are then printf patterns "
                         "of the frame number, such as /tmp/original_%%04d.png, /tmp/encoded_%%04d and "
                         "/tmp/decoded_%%04d.png (default: one image)")
+    p.add_argument("--ssim", action="store_true", default=False,
+                   help="Not in the reference: also print the SSIM (11 x 11 integer Gaussian window, windows "
+                        "wholly inside the image; grey or RGB images of at least 11 x 11) (default: \"False\")")
     return p
 
 
@@ -480,6 +483,9 @@ def rd_curve_parser(description: str = "Rate-distortion curve of the default cha
                    help="Use perceptual quantization (default: \"False\")", default=False)
     p.add_argument("-x", "--disable_subbands", action="store_true",
                    help="Disable the coefficients reordering in subbands (default: \"False\")", default=False)
+    p.add_argument("--ssim", action="store_true", default=False,
+                   help="Also measure the SSIM of every frame (11 x 11 integer Gaussian window; frames of at least "
+                        "11 x 11): `SSIM x.xxxx` on each line, `ssim` in --json (default: \"False\")")
     p.add_argument("--json", action="store_true", help="Print one JSON line with the per-frame values of every Q")
     return p
 

@@ -108,6 +108,7 @@ class Result:
     shape: tuple
     rmse: float
     psnr: float = float("nan")
+    ssim: float | None = field(default=None, repr=False, compare=False)   # evaluate(ssim=True): mean over channels
 
     @property
     def number_of_pixels(self) -> int:
@@ -143,6 +144,8 @@ class Result:
         out.append(f"RDE: Images shape: {self.shape}")
         out.append(f"RDE: Distortion (RMSE): {self.rmse:.2f}")
         out.append(f"RDE: J = R + D = {self.J:.2f}")
+        if self.ssim is not None:       # not in RDE.py: one further line, after its own
+            out.append(f"RDE: SSIM: {self.ssim:.4f}")
         return out
 
 
@@ -152,14 +155,20 @@ def _sizes(original: str, codestream: str, decoded: str):
 
 
 def evaluate(original: str = "/tmp/original.png", codestream: str = "/tmp/encoded*",
-             decoded: str = "/tmp/decoded.png") -> Result:
-    """RDE.py's main() for one image; raises ShapeMismatch where RDE.py prints its error."""
+             decoded: str = "/tmp/decoded.png", ssim: bool = False) -> Result:
+    """RDE.py's main() for one image; raises ShapeMismatch where RDE.py prints its error.  With `ssim` the result
+    carries the frame's SSIM (distortion.ssim: grey or RGB images of at least 11 x 11, ValueError otherwise)."""
     a, b = read_image(original), read_image(decoded)
     if a.shape != b.shape:
         raise ShapeMismatch(a.shape, b.shape)
+    if ssim:
+        DS._check_ssim_shape(1, *_hwc(a))
     m = DS.measure(a, b)
     ob, files, lengths, db = _sizes(original, codestream, decoded)
-    return Result(original, decoded, files, lengths, ob, db, tuple(a.shape), float(m.rmse()[0]), float(m.psnr()[0]))
+    res = Result(original, decoded, files, lengths, ob, db, tuple(a.shape), float(m.rmse()[0]), float(m.psnr()[0]))
+    if ssim:
+        res.ssim = float(DS.ssim(a, b).per_frame()[0])
+    return res
 
 
 @dataclass
@@ -172,24 +181,28 @@ class SequenceResult:
     psnr: np.ndarray
     launches: int = 0                 # kernel launches used (one per batch of equal shapes)
     means: dict = field(default_factory=dict)
+    ssim: np.ndarray | None = field(default=None, repr=False, compare=False)   # evaluate_sequence(ssim=True)
 
     def lines(self) -> list:
         out = []
         for i, r in enumerate(self.frames):
             out.append(f"RDE: Frame {i}: {r.codestream_bytes} bytes ({r.codestream_bpp:.2f}) bits/pixel, "
-                       f"RMSE {r.rmse:.2f}, PSNR {r.psnr:.2f} dB, J = {r.J:.2f}")
+                       f"RMSE {r.rmse:.2f}, PSNR {r.psnr:.2f} dB, J = {r.J:.2f}"
+                       + ("" if r.ssim is None else f", SSIM {r.ssim:.4f}"))
         m = self.means
         out.append(f"RDE: Mean of {len(self.frames)} frames: {m['bytes']:.1f} bytes ({m['bpp']:.2f}) bits/pixel, "
-                   f"RMSE {m['rmse']:.2f}, PSNR {m['psnr']:.2f} dB, J = {m['J']:.2f}")
+                   f"RMSE {m['rmse']:.2f}, PSNR {m['psnr']:.2f} dB, J = {m['J']:.2f}"
+                   + (f", SSIM {m['ssim']:.4f}" if "ssim" in m else ""))
         return out
 
 
 def evaluate_sequence(original_pattern: str, decoded_pattern: str, codestream_pattern: str, n: int, batch: int = 16,
-                      io_threads: int = 8) -> SequenceResult:
+                      io_threads: int = 8, ssim: bool = False) -> SequenceResult:
     """RDE for frames 0 .. n-1 of an III or IPP run.  The three patterns are printf patterns of the frame number
     (/tmp/original_%04d.png, /tmp/decoded_%04d.png, /tmp/encoded_%04d); a frame's code-stream files follow
     RDE.py's prefix rule applied to its formatted pattern.  `io_threads` threads read the images; consecutive
-    frames of one shape, `batch` at most, are uploaded together and measured by one kernel launch."""
+    frames of one shape, `batch` at most, are uploaded together and measured by one kernel launch.  With `ssim`
+    every frame's SSIM is measured too (one further launch a batch) and reported per frame and as a mean."""
     n, batch = int(n), max(1, int(batch))
     if n < 1:
         raise ValueError(f"number of frames must be at least 1 (got {n})")
@@ -211,14 +224,18 @@ def evaluate_sequence(original_pattern: str, decoded_pattern: str, codestream_pa
         j = i + 1
         while j < n and j - i < batch and pairs[j][0].shape == pairs[i][0].shape:
             j += 1
-        m = DS.measure(np.stack([pairs[t][0].reshape(_hwc(pairs[t][0])) for t in range(i, j)]),
-                       np.stack([pairs[t][1].reshape(_hwc(pairs[t][1])) for t in range(i, j)]))
+        sa = np.stack([pairs[t][0].reshape(_hwc(pairs[t][0])) for t in range(i, j)])
+        sb = np.stack([pairs[t][1].reshape(_hwc(pairs[t][1])) for t in range(i, j)])
+        m = DS.measure(sa, sb)
         launches += 1
         rm, ps = m.rmse(), m.psnr()
+        ss = DS.ssim(sa, sb).per_frame() if ssim else None
         for t in range(i, j):
             ob, files, lengths, db = sizes[t]
             results[t] = Result(names[t][0], names[t][1], files, lengths, ob, db, tuple(pairs[t][0].shape),
                                 float(rm[t - i]), float(ps[t - i]))
+            if ssim:
+                results[t].ssim = float(ss[t - i])
         i = j
     by = np.array([r.codestream_bytes for r in results], np.int64)
     bpp = np.array([r.codestream_bpp for r in results])
@@ -226,22 +243,29 @@ def evaluate_sequence(original_pattern: str, decoded_pattern: str, codestream_pa
     psnr = np.array([r.psnr for r in results])
     means = dict(bytes=float(by.mean()), bpp=float(bpp.mean()), rmse=float(rmse.mean()), psnr=float(psnr.mean()),
                  J=float((bpp + rmse).mean()))
-    return SequenceResult(results, by, bpp, rmse, psnr, launches, means)
+    if not ssim:
+        return SequenceResult(results, by, bpp, rmse, psnr, launches, means)
+    per_frame = np.array([r.ssim for r in results])
+    means["ssim"] = float(per_frame.mean())
+    return SequenceResult(results, by, bpp, rmse, psnr, launches, means, per_frame)
 
 
 def _hwc(a: np.ndarray):
     return a.shape if a.ndim == 3 else a.shape + (1,)
 
 
-def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0) -> list:
+def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False) -> list:
     """The rate-distortion curve of the default chain (2D-DCT.py: YCoCg, B x B DCT, deadzone, -c TIFF) over the
     quantization steps Qs, with the n equal-shape H x W x 3 u8 frames uploaded once.  Per Q, on the device:
     dct.encode_device, the deflate of the TIFF strips for their sizes (zlib_gpu.tiff_sizes_device), dct.decode_device
     and vcf_distortion_u8 against the resident originals; the strip sizes and the distortion records are all that
     comes back.  -> per Q a dict of Q and the per-frame arrays bytes (len(tif) + 12 for _shape.bin: what RDE.py
     sums for /tmp/encoded*), bpp, rmse, psnr and J = bpp + rmse -- the numbers encode_fn, decode_fn and RDE give
-    through files.  Raises NotImplementedError where the GPU deflate does not cover the frame (rows over 64 KB):
-    the host TIFF writer's sizes would be the same, but a silent change of path is not this function's to make."""
+    through files.  With `ssim` every dict also has ssim, the per-frame SSIM (distortion.Ssim.per_frame) of the
+    resident originals against the resident reconstructions, measured by vcf_ssim_u8 right after the distortion;
+    only its records come back too.  Frames under 11 x 11 then raise ValueError.  Raises NotImplementedError where
+    the GPU deflate does not cover the frame (rows over 64 KB): the host TIFF writer's sizes would be the same, but a
+    silent change of path is not this function's to make."""
     from .. import dct as D
     from .. import zlib_gpu
     f = np.asarray(frames)
@@ -255,6 +279,8 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0) -> list:
     n, H, W, _ = f.shape
     if n < 1 or H < 1 or W < 1:
         raise ValueError(f"no samples in frames of shape {f.shape}")
+    if ssim:
+        DS._check_ssim_shape(n, H, W, 3)
     Hp, Wp = D.padded_shape(H, W, block_size)
     if not zlib_gpu.covers((Hp, Wp, 3), 1):
         raise NotImplementedError(f"-c TIFF strips of {Hp} x {Wp} x 3 index frames are beyond the GPU deflate "
@@ -266,6 +292,9 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0) -> list:
         k, rec = DeviceBuffer(n * Hp * Wp * 3), DeviceBuffer(n * H * W * 3)
         out = DeviceBuffer(n * 3 * DS.RECORD.itemsize)
         bufs += [src, k, rec, out]
+        if ssim:
+            sout = DeviceBuffer(n * 3 * DS.SSIM_RECORD.itemsize)
+            bufs.append(sout)
         curve = []
         for Q in Qs:
             Q = int(Q)
@@ -273,11 +302,15 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0) -> list:
             tif = zlib_gpu.tiff_sizes_device(k, n, (Hp, Wp, 3), np.uint8, stream=st)
             D.decode_device(k, n, H, W, Q, flags, out=rec, stream=st, block_size=block_size)
             DS.sse_device(src, rec, n, H, W, 3, out, st)
+            if ssim:
+                DS.ssim_device(src, rec, n, H, W, 3, sout, st)
             m = DS.records(out, n, 3, H * W, st)
             by = tif + 12
             bpp = by * 8 / (H * W)
             rmse = m.rmse()
             curve.append(dict(Q=Q, bytes=by, bpp=bpp, rmse=rmse, psnr=m.psnr(), J=bpp + rmse))
+            if ssim:
+                curve[-1]["ssim"] = DS.ssim_records(sout, n, 3, st).per_frame()
         return curve
     finally:
         st.synchronize()
@@ -288,16 +321,21 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0) -> list:
 
 # ---- the programs ------------------------------------------------------------------
 def main(argv=None) -> int:
-    """`python RDE.py [-o ...] [-c ...] [-d ...] [-N n]`; the exit status."""
+    """`python RDE.py [-o ...] [-c ...] [-d ...] [-N n] [--ssim]`; the exit status."""
+    import sys
+
     from . import parser as P
     args = P.rde_parser().parse_args(argv)
     try:
         if args.number_of_frames is not None:
-            res = evaluate_sequence(args.original, args.decoded, args.codestream, args.number_of_frames)
+            res = evaluate_sequence(args.original, args.decoded, args.codestream, args.number_of_frames, ssim=args.ssim)
         else:
-            res = evaluate(args.original, args.codestream, args.decoded)
+            res = evaluate(args.original, args.codestream, args.decoded, ssim=args.ssim)
     except ShapeMismatch as e:
         print("\n".join(e.lines()))
+        return 1
+    except DS.SsimShapeError as e:       # --ssim on frames it is not defined on: say so, measure nothing else
+        print(f"RDE: {e}", file=sys.stderr)
         return 1
     print("\n".join(res.lines()))
     return 0
@@ -314,20 +352,26 @@ def _curve_frames(original: str, n):
 
 
 def curve_main(argv=None) -> int:
-    """`python RD-curve.py -o ... -q 8,16,32 [-N n] [-B b] [-p] [-x] [--json]`."""
+    """`python RD-curve.py -o ... -q 8,16,32 [-N n] [-B b] [-p] [-x] [--ssim] [--json]`."""
     import json
+    import sys
 
     from .. import dct as D
     from . import parser as P
     args = P.rd_curve_parser().parse_args(argv)
     Qs = [int(q) for q in str(args.QSS).split(",") if q.strip()]
     frames = _curve_frames(args.original, args.number_of_frames)
-    curve = rd_curve(frames, Qs, int(args.block_size_DCT), D.flags_from(args.disable_subbands, args.perceptual_quantization))
+    try:
+        curve = rd_curve(frames, Qs, int(args.block_size_DCT),
+                         D.flags_from(args.disable_subbands, args.perceptual_quantization), ssim=args.ssim)
+    except DS.SsimShapeError as e:
+        print(f"RD: {e}", file=sys.stderr)
+        return 1
     if args.json:
         print(json.dumps([{k: (v if k == "Q" else np.asarray(v).tolist()) for k, v in c.items()} for c in curve]))
         return 0
     for c in curve:
         print(f"RD: Q = {c['Q']}: {c['bytes'].mean():.1f} bytes ({c['bpp'].mean():.2f}) bits/pixel, "
               f"RMSE {c['rmse'].mean():.2f}, PSNR {c['psnr'].mean():.2f} dB, J = {c['J'].mean():.2f} "
-              f"(means of {len(c['bytes'])} frames)")
+              + (f"SSIM {c['ssim'].mean():.4f} " if "ssim" in c else "") + f"(means of {len(c['bytes'])} frames)")
     return 0

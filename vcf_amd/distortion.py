@@ -8,6 +8,12 @@ stack (N x H x W x C).  RMSE = sqrt(float64(sum of sse) / (H * W * C)): the
 integer sum is exact, so the only roundings are the division and the root.
 There is no CPU path: the arithmetic runs in libvcf_amd.so and is stated in
 include/vcf_amd.h.
+
+vcf_ssim_u8 gives, per frame and channel, the SSIM in the integer form of
+DESIGN.md §4.15 (C = 1 or 3, frames of at least 11 x 11): the exact integer sum
+and the minimum of k = rint(q * 2^30) over the 11 x 11 windows wholly inside
+the frame.  ssim_device and ssim_records work on DeviceBuffers, ssim on host
+arrays; SSIM = sum_k / (windows * 2^30), divided in float64 here.
 """
 from __future__ import annotations
 
@@ -130,3 +136,83 @@ def rmse(a, b):
 def psnr(a, b):
     """10 log10(255^2 / mse), inf at mse 0."""
     return _reduce(measure(a, b).psnr(), a)
+
+
+# ---- SSIM (vcf_ssim.hip; DESIGN.md §4.15) -------------------------------------------
+# vcf_ssim_record (include/vcf_amd.h)
+SSIM_RECORD = np.dtype([("sum_k", np.int64), ("windows", np.uint64), ("min_k", np.int64)])
+SSIM_WINDOW = 11           # the footprint; its outer taps are 0, so the support is 9 x 9
+SSIM_ONE = 1 << 30         # k = rint(q * 2^30)
+
+
+@dataclass
+class Ssim:
+    """Per frame and channel (n x C arrays), exact integers: the sum and the minimum over the windows of
+    k = rint(q * 2^30), q the window's SSIM in the integer form of DESIGN.md §4.15."""
+    sum_k: np.ndarray      # int64
+    min_k: np.ndarray      # int64
+    windows: int           # (H - 10) * (W - 10): windows wholly inside one frame
+
+    def per_channel(self) -> np.ndarray:
+        """n x C float64: sum_k / (windows * 2^30), one division of exact integers."""
+        return self.sum_k.astype(np.float64) / float(self.windows * SSIM_ONE)
+
+    def per_frame(self) -> np.ndarray:
+        """n float64, the mean over the channels: (sum over c of sum_k) / (C * windows * 2^30)."""
+        C = self.sum_k.shape[1]
+        return self.sum_k.sum(axis=1, dtype=np.int64).astype(np.float64) / float(C * self.windows * SSIM_ONE)
+
+
+class SsimShapeError(ValueError):
+    """Frames the SSIM is not defined on: smaller than its window, or neither 1 nor 3 channels."""
+
+
+def _check_ssim_shape(n: int, H: int, W: int, C: int) -> None:
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise SsimShapeError(f"the SSIM window is {SSIM_WINDOW} x {SSIM_WINDOW}: frames of {H} x {W} hold none")
+    if C not in (1, 3):
+        raise SsimShapeError(f"SSIM is measured on 1 or 3 channels, got {C}")
+    if n < 1:
+        raise ValueError(f"SSIM needs at least one frame, got {n}")
+
+
+def ssim_device(a: DeviceBuffer, b: DeviceBuffer, n: int, H: int, W: int, C: int, out: DeviceBuffer | None = None,
+                stream=None) -> DeviceBuffer:
+    """n frames of H x W x C u8 in `a` against those in `b` -> n x C records (SSIM_RECORD) in HBM, enqueued on
+    `stream`.  The call sets the records itself.  C is 1 or 3, H and W at least 11 (ValueError otherwise)."""
+    n, H, W, C = int(n), int(H), int(W), int(C)
+    _check_ssim_shape(n, H, W, C)
+    check_input(a, n * H * W * C)
+    check_input(b, n * H * W * C)
+    out = output(out, n * C * SSIM_RECORD.itemsize)
+    call("vcf_ssim_u8", a.ptr, b.ptr, n, H, W, C, out.ptr, _h(stream))
+    return out
+
+
+def ssim_records(buf: DeviceBuffer, n: int, C: int, stream=None) -> Ssim:
+    """Download the n x C records of a ssim_device call (synchronises `stream`)."""
+    rec = np.zeros((int(n), int(C)), SSIM_RECORD)
+    buf.download(rec, stream)
+    if stream is not None:
+        stream.synchronize()
+    return Ssim(rec["sum_k"].copy(), rec["min_k"].copy(), int(rec["windows"][0, 0]))
+
+
+def ssim(a, b) -> Ssim:
+    """The SSIM records of host u8 frames a against b: H x W, H x W x C or N x H x W x C, equal shapes."""
+    shape_a, shape_b = np.shape(a), np.shape(b)
+    fa, _ = _frames(a, "a")
+    fb, _ = _frames(b, "b")
+    if shape_a != shape_b:
+        raise ValueError(f"shapes differ: {shape_a} and {shape_b}")
+    n, H, W, C = fa.shape
+    _check_ssim_shape(n, H, W, C)
+    da = db = out = None
+    try:
+        da, db = DeviceBuffer.from_array(fa), DeviceBuffer.from_array(fb)
+        out = ssim_device(da, db, n, H, W, C)
+        return ssim_records(out, n, C)
+    finally:
+        for buf in (da, db, out):
+            if buf is not None:
+                buf.free()
