@@ -28,7 +28,7 @@ SOURCES = ["vcf_runtime.hip", "vcf_dct_dz.hip", "vcf_dct_any.hip", "vcf_quant.hi
 HEADERS = ["vcf_dct8.h", "vcf_dct_block.h", "vcf_block_tile.h", "vcf_internal.h", "vcf_wavelets.h", "vcf_pocketfft.h", "vcf_pocketfft_tables.h",
            "vcf_pocketfft_rt.h", "vcf_pocketfft_blue.h", "vcf_sincos.h", "vcf_pipeline.h", "vcf_dwt_band.h", "vcf_idwt_line.h", "vcf_idwt_band21.h",
            "vcf_dwt_lift.h", "vcf_band_cut.h",
-           "vcf_deflate.h"]
+           "vcf_deflate.h", "vcf_cbaac_coder.h"]
 OBJDIR = os.path.join(ROOT, "build", "obj")
 ARCH = os.environ.get("VCF_OFFLOAD_ARCH", "gfx950")
 

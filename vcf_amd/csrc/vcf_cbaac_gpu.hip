@@ -13,39 +13,39 @@
 // exactly what the serial coder (vcf_cbaac_encode) writes for that segment
 // alone, and the container (vcf_amd/tcbaac.py) records each segment's size.
 //
-// Mapping: one wave per segment; the 64 lanes share one model.
-//   - Order 0: the cumulative table C[0..256) of the model lives in VGPRs,
-//     lane l holding C[4l .. 4l+3]; C[256] = total is wave-uniform.
-//     get_range(s) (:40-41) is two v_readlane; update(s) (:32-36) adds 1 to
-//     C[t] for t > s in every lane (4 compares, no cross-lane work); the
-//     rescale (every ~16 k symbols: stale total >= 16384, f = (f >> 1) + 1)
-//     rebuilds C with one wave prefix scan.  The decoder's
-//     get_symbol_from_scaled_value (:43-47) becomes one ballot over the
-//     lanes' interval ends (see the decode kernel).
-//   - Order 1: the 256 context models (one per previous symbol) as 16-bit
-//     cumulative tables in LDS (128 KiB + totals), the current context's row
-//     read into the same four VGPRs per lane and written back after the
-//     update.
-//   - The coder state (low, high, pending bits, the bit writer) is
-//     wave-uniform; floor(range * c / total) is a float64 multiply by an
-//     estimated 1/total plus an exact correction (operands < 2^47).  Bits are packed MSB-first into
-//     words that lane 0 stores (vector stores); symbols stream in 256 at a
-//     time (one dword per lane, the next chunk prefetched).
-// A second pass packs the segments back to back (a scan of their sizes and a
-// copy), so only the compressed bytes need to leave HBM.
+// Three kernel families run that algorithm and write the same bytes:
+//   - One WAVE per segment (cbaac_tiled_encode_kernel / _decode_kernel): the 64 lanes share one model and a
+//     wave-uniform coder state.  Order 0: the cumulative table C[0..256) lives in VGPRs, lane l holding
+//     C[4l .. 4l+3]; get_range(s) (:40-41) is two v_readlane, update(s) (:32-36) four compares per lane, the
+//     rescale (stale total >= 16384, f = (f >> 1) + 1) one wave prefix scan, and the decoder's
+//     get_symbol_from_scaled_value (:43-47) one ballot over the lanes' interval ends (decode_step).  Order 1:
+//     256 such tables in LDS, the current context's row in the same VGPRs.  Lane 0 stores the words of
+//     MSB-first bits; symbols stream in 256 at a time (one dword per lane, the next chunk prefetched).
+//   - One LANE per segment (cbaac_lane_encode_kernel / _decode_kernel, order 0): a wave codes 64 segments at
+//     once, every lane with its own two-level model in LDS and its own coder state; the library takes it
+//     from kLaneMinEncode / kLaneMinDecode segments on.
+//   - One wave per 2-D TILE (cbaac2d_*_kernel over frames, cbaac2d_*_planes_kernel over a list of arrays,
+//     container version 4): the wave kernels' model, one of 16 chosen by the left and upper neighbours.
+// The coder's step -- interval narrowing (floor(range * c / total) as a float64 multiply by an estimated
+// 1/total plus an exact correction), renormalisation, the encoder's emission and flush, the decoder's window,
+// the bit writer -- is vcf_cbaac_coder.h's for all of them; here are each family's model, loads and stores.
+// A second pass packs the segments back to back (a scan of their sizes and a copy), so only the compressed
+// bytes need to leave HBM.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
 #include "vcf_amd.h"
+#include "vcf_cbaac_coder.h"
 #include "vcf_internal.h"
 
 namespace vcf {
 namespace {
 
+using namespace a8;   // the coder's step (vcf_cbaac_coder.h)
+
 constexpr uint32_t kMaxFreq = 16384;   // AdaptiveModel(max_freq=16384), CBAAC.py:18
-constexpr uint32_t kQ1 = 0x40000000u;
 constexpr int kChunk = 256;            // symbols (or bytes) per wave load: one dword per lane
 
 __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane)
@@ -77,7 +77,15 @@ __device__ __forceinline__ void model_reset(Model &m, uint32_t lane)
 constexpr uint32_t kPriorScale = 8192;   // prior total <= 256 + 8192 < max_freq
 constexpr int32_t kMaxClasses = 256;      // prior rows per frame (container version 3)
 
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane);
+__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane)
+{
+    uint32_t incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(incl, d, 64);
+        if (lane >= (uint32_t)d) incl += o;
+    }
+    return incl - v;
+}
 
 __device__ __forceinline__ void model_reset_prior(Model &m, const uint16_t *__restrict__ prior, uint32_t lane)
 {
@@ -112,16 +120,6 @@ __device__ __forceinline__ void model_range(const Model &m, uint32_t s, uint32_t
     const uint32_t j = s & 3;
     lo = (uint32_t)(q.w >> (16 * j)) & 0xFFFFu;
     hi = j == 3 ? q.next : (uint32_t)(q.w >> (16 * j + 16)) & 0xFFFFu;
-}
-
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane)
-{
-    uint32_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += o;
-    }
-    return incl - v;
 }
 
 // update(s) (CBAAC.py:32-36): freqs[s] += 1, i.e. C[t] += 1 for t > s; if the
@@ -205,20 +203,7 @@ __device__ __forceinline__ void tables_write(Tables &t, uint32_t ctx, uint32_t l
     if (lane == 0) t.total[ctx] = m.total;
 }
 
-// ---- the A8 coder's arithmetic ---------------------------------------------------------
-// floor(a / t) for integers a < 2^47, 0 < t <= 2^19 held exactly in doubles,
-// given inv ~= 1/t (relative error < 2^-50): q = trunc(a * inv) is within 1
-// of the floor, r = a - q t is exact (an fma of integers < 2^47) and lies in
-// (-t, 2t), and floor(r * inv + 2^-20) is the step (-1, 0 or +1) that fixes
-// q: r / t = m + j/t with j in 0..t-1, and 2^-20 is below 1/t
-// (t <= 2^19) and above the error of r * inv.
-__device__ __forceinline__ double floordiv(double a, double t, double inv)
-{
-    const double q = __builtin_trunc(a * inv);
-    const double r = __builtin_fma(-q, t, a);
-    return q + __builtin_floor(__builtin_fma(r, inv, 0x1p-20));
-}
-
+// ---- the A8 coder (vcf_cbaac_coder.h) with a wave-uniform state -------------------------
 // 1/t for 1 <= t < 2^33: the hardware estimate and two Newton steps
 // (relative error far below the 2^-50 floordiv needs).
 __device__ __forceinline__ double rcp_nr(double t)
@@ -229,82 +214,28 @@ __device__ __forceinline__ double rcp_nr(double t)
     return x;
 }
 
-// MSB-first bit writer (bitarray endian='big'); lane 0 stores whole words.
-// acc holds nb < 32 pending bits at its top.
-struct BitWriter {
+// the wave's bit writer: lane 0 stores the words
+struct Lane0Store {
     uint32_t *out;
-    uint64_t acc = 0;
-    uint32_t nb = 0;
-    uint64_t words = 0;
-
-    // append the top k bits of v (1 <= k <= 32)
-    __device__ __forceinline__ void bits(uint32_t v, uint32_t k, uint32_t lane)
+    uint32_t lane;
+    __device__ __forceinline__ void operator()(uint64_t i, uint32_t word) const
     {
-        if (k < 32) v &= ~(0xFFFFFFFFu >> k);
-        acc |= (uint64_t)v << (32 - nb);
-        nb += k;
-        if (nb >= 32) {
-            if (lane == 0) out[words] = __builtin_bswap32((uint32_t)(acc >> 32));
-            ++words;
-            acc <<= 32;
-            nb -= 32;
-        }
-    }
-    __device__ __forceinline__ void run(uint32_t bit, uint64_t count, uint32_t lane)
-    {
-        const uint32_t v = bit ? 0xFFFFFFFFu : 0u;
-        for (; count >= 32; count -= 32) bits(v, 32, lane);
-        if (count) bits(v, (uint32_t)count, lane);
-    }
-    __device__ __forceinline__ uint64_t finish(uint32_t lane)
-    {
-        if (nb && lane == 0) out[words] = __builtin_bswap32((uint32_t)(acc >> 32));
-        return words * 32 + nb;
+        if (lane == 0) out[i] = word;
     }
 };
+using WaveBits = BitWriter<uint64_t, Lane0Store>;
 
 // Encoder state: the interval and the pending (underflow) bits.
 struct Encoder {
     uint32_t low = 0, high = 0xFFFFFFFFu;
     uint64_t pending = 0;
 
-    // interval update + renormalisation of the A8 coder (vcf_cbaac.cpp's loop,
-    // done in one step: the loop emits the common leading bits of low and
-    // high, each followed by the pending bits after the first, then counts
-    // the underflow steps while low = 01.. and high = 10..)
-    __device__ __forceinline__ void code(uint32_t lo, uint32_t hi, double tot, double inv, BitWriter &w,
-                                         uint32_t lane)
+    __device__ __forceinline__ void code(uint32_t lo, uint32_t hi, double tot, double inv, WaveBits &w)
     {
-        const double rng = (double)(high - low) + 1.0;
-        const double qh = floordiv(rng * (double)hi, tot, inv);
-        const double ql = floordiv(rng * (double)lo, tot, inv);
-        high = low + (uint32_t)(qh - 1.0);
-        low = low + (uint32_t)ql;
-        const uint32_t d = __builtin_clz(low ^ high);   // high > low: d <= 31
-        if (d) {
-            const uint32_t b = low >> 31;
-            w.bits(low, 1, lane);
-            w.run(b ^ 1u, pending, lane);
-            pending = 0;
-            if (d > 1) w.bits(low << 1, d - 1, lane);
-            low <<= d;
-            high = (high << d) | ((1u << d) - 1u);
-        }
-        const uint32_t x = (low << 1) & ~(high << 1);
-        const uint32_t p = __builtin_clz(~x);
-        if (p) {
-            pending += p;
-            low = (low << p) & 0x7FFFFFFFu;
-            high = (high << p) | ((1u << p) - 1u) | 0x80000000u;
-        }
+        narrow(low, high, lo, hi, tot, inv);
+        encode_renorm(low, high, pending, w);
     }
-    // flush (CBAAC.py:130 -> A8): one more pending bit and a disambiguating bit
-    __device__ __forceinline__ void flush(BitWriter &w, uint32_t lane)
-    {
-        const uint32_t b = low < kQ1 ? 0u : 1u;
-        w.bits(b << 31, 1, lane);
-        w.run(b ^ 1u, pending + 1, lane);
-    }
+    __device__ __forceinline__ void flush(WaveBits &w) { encode_flush(w, low, pending); }
 };
 
 // Four symbols per lane.  Segment starts are multiples of 256 symbols from
@@ -320,8 +251,6 @@ __device__ __forceinline__ uint32_t load_sym4(const uint8_t *p, int64_t off, int
         if (i + j < len) v |= (uint32_t)p[i + j] << (8 * j);
     return v;
 }
-
-__device__ __forceinline__ double rcp_exact(uint32_t t) { return rcp_nr((double)t); }
 
 // Frames of a batch (blockIdx.y = frame): frame f's symbols at sym + f *
 // sym_stride, its prior at prior + f * prior_stride (0: one prior for all),
@@ -369,8 +298,7 @@ __global__ __launch_bounds__(64) void cbaac_tiled_encode_kernel(const uint8_t *_
     }
     uint32_t ctx = 0;
 
-    BitWriter w;
-    w.out = slots + seg * slot_words;
+    WaveBits w{{slots + seg * slot_words, lane}};
     Encoder e;
 
     const bool aligned = (reinterpret_cast<uintptr_t>(sym) & 3) == 0;
@@ -382,7 +310,7 @@ __global__ __launch_bounds__(64) void cbaac_tiled_encode_kernel(const uint8_t *_
             const uint32_t s = (rl(cur, k >> 2) >> (8 * (k & 3))) & 255u;
             if constexpr (ORDER == 1) tables_read(tabs[0], ctx, lane, m);
             const uint32_t tot = m.total;
-            const double inv = rcp_exact(tot);
+            const double inv = rcp_nr((double)tot);
             uint32_t lo, hi;
             model_range(m, s, lo, hi);
             if constexpr (TRACE) {
@@ -393,7 +321,7 @@ __global__ __launch_bounds__(64) void cbaac_tiled_encode_kernel(const uint8_t *_
                     t[2] = (int32_t)tot;
                 }
             }
-            e.code(lo, hi, (double)tot, inv, w, lane);
+            e.code(lo, hi, (double)tot, inv, w);
             model_update(m, s, lane);
             if constexpr (ORDER == 1) {
                 tables_write(tabs[0], ctx, lane, m);
@@ -402,8 +330,8 @@ __global__ __launch_bounds__(64) void cbaac_tiled_encode_kernel(const uint8_t *_
         }
         cur = nxt;
     }
-    e.flush(w, lane);
-    const uint64_t bits = w.finish(lane);
+    e.flush(w);
+    const uint64_t bits = w.finish();
     if (lane == 0) seg_bits[seg] = (int64_t)bits;
 }
 
@@ -456,6 +384,44 @@ struct BitReader {
     }
 };
 
+struct WaveGet {   // the coder's reader interface: get(k)
+    BitReader &br;
+    uint32_t lane;
+    __device__ __forceinline__ uint32_t get(uint32_t k) { return br.get(k, lane); }
+};
+
+// One symbol of the A8 decoder with model m (the 2-D tile kernels call it; cbaac_tiled_decode_kernel
+// carries a written-out copy, see there).  The decoder picks s with C[s] <=
+// floor(((T + 1) total - 1) / range) < C[s+1], T = value - low; for integers
+// that is floor(range C[s] / total) <= T < floor(range C[s+1] / total), and
+// those floors are the new interval's ends: every lane computes them for its
+// four counts, a ballot finds the lane, no division by range.
+__device__ __forceinline__ uint32_t decode_step(Model &m, BitReader &br, uint32_t &low, uint32_t &high,
+                                                uint32_t &value, uint32_t lane)
+{
+    const double tot = (double)m.total;
+    const double inv = rcp_nr(tot);
+    const uint32_t span = high - low;                 // range - 1
+    const double rng = (double)span + 1.0;
+    const uint32_t T = value - low;
+    const uint32_t f0 = (uint32_t)floordiv(rng * (double)(m.p0 & 0xFFFFu), tot, inv);
+    const uint32_t f1 = (uint32_t)floordiv(rng * (double)(m.p0 >> 16), tot, inv);
+    const uint32_t f2 = (uint32_t)floordiv(rng * (double)(m.p1 & 0xFFFFu), tot, inv);
+    const uint32_t f3 = (uint32_t)floordiv(rng * (double)(m.p1 >> 16), tot, inv);
+    const uint32_t L = (uint32_t)__popcll(__ballot(f0 <= T)) - 1;   // f0 increases with the lane
+    const uint32_t g0 = rl(f0, L), g1 = rl(f1, L), g2 = rl(f2, L), g3 = rl(f3, L);
+    const uint32_t g4m1 = L == 63 ? span : rl(f0, (L + 1) & 63) - 1;   // floor(range C[4L+4] / total) - 1
+    const uint32_t j = (T >= g1 ? 1u : 0u) + (T >= g2 ? 1u : 0u) + (T >= g3 ? 1u : 0u);
+    const uint32_t s = 4 * L + j;
+    const uint32_t ql = j == 0 ? g0 : j == 1 ? g1 : j == 2 ? g2 : g3;
+    const uint32_t qhm1 = j == 0 ? g1 - 1 : j == 1 ? g2 - 1 : j == 2 ? g3 - 1 : g4m1;
+    narrow_floored(low, high, ql, qhm1);
+    WaveGet bits{br, lane};
+    decode_renorm(low, high, value, bits);
+    model_update(m, s, lane);
+    return s;
+}
+
 template <int ORDER>
 __global__ __launch_bounds__(64) void cbaac_tiled_decode_kernel(const uint8_t *__restrict__ in,
                                                                 const int64_t *__restrict__ offs, int64_t n,
@@ -485,12 +451,13 @@ __global__ __launch_bounds__(64) void cbaac_tiled_decode_kernel(const uint8_t *_
     }
     uint32_t ctx = 0;
 
-    BitReader br;
-    br.src = in + offs[seg];
-    br.nbytes = offs[seg + 1] - offs[seg];
+    BitReader br{in + offs[seg], offs[seg + 1] - offs[seg]};
     br.start(lane);
     uint32_t low = 0, high = 0xFFFFFFFFu, value = br.get(32, lane);
 
+    // The loop body is decode_step written out, renormalisation included.  Called as decode_step, or with
+    // vcf_cbaac_coder.h's renorm() in its place, this kernel alone is compiled to another instruction schedule
+    // and decodes 0.4-1.4 % slower (measured); the 2-D kernels keep their schedule through decode_step.
     uint32_t obuf = 0, acc = 0;
     for (int64_t i = 0; i < len; ++i) {
         if constexpr (ORDER == 1) tables_read(tabs[0], ctx, lane, m);
@@ -498,11 +465,6 @@ __global__ __launch_bounds__(64) void cbaac_tiled_decode_kernel(const uint8_t *_
         const double inv = rcp_nr(tot);
         const uint32_t span = high - low;                 // range - 1
         const double rng = (double)span + 1.0;
-        // The A8 decoder picks s with C[s] <= floor(((T + 1) total - 1) / range)
-        // < C[s+1], T = value - low; for integers that is
-        // floor(range C[s] / total) <= T < floor(range C[s+1] / total), and
-        // those floors are the new interval's ends: every lane computes them
-        // for its four counts, a ballot finds the lane, no division by range.
         const uint32_t T = value - low;
         const uint32_t f0 = (uint32_t)floordiv(rng * (double)(m.p0 & 0xFFFFu), tot, inv);
         const uint32_t f1 = (uint32_t)floordiv(rng * (double)(m.p0 >> 16), tot, inv);
@@ -515,7 +477,7 @@ __global__ __launch_bounds__(64) void cbaac_tiled_decode_kernel(const uint8_t *_
         const uint32_t s = 4 * L + j;
         const uint32_t ql = j == 0 ? g0 : j == 1 ? g1 : j == 2 ? g2 : g3;
         const uint32_t qhm1 = j == 0 ? g1 - 1 : j == 1 ? g2 - 1 : j == 2 ? g3 - 1 : g4m1;
-        high = low + qhm1;
+        high = low + qhm1;                              // narrow_floored and decode_renorm, written out
         low = low + ql;
         const uint32_t d = __builtin_clz(low ^ high);
         if (d) {
@@ -777,30 +739,12 @@ __device__ __attribute__((noinline)) uint32_t lane_model_rescale(LaneLds &L, uin
     return run;
 }
 
-// per-lane MSB-first bit writer: acc holds nb < 32 pending bits at its top, whole
-// words go to the lane's own slot (bitarray endian='big')
-struct LaneBits {
+// a lane's bit writer: every lane stores the words of its own slot
+struct OwnStore {
     uint32_t *out;
-    uint64_t acc = 0;
-    uint32_t nb = 0, words = 0;
-    __device__ __forceinline__ void bits(uint32_t v, uint32_t k)   // the top k bits of v, 1 <= k <= 32
-    {
-        if (k < 32) v &= ~(0xFFFFFFFFu >> k);
-        acc |= (uint64_t)v << (32 - nb);
-        nb += k;
-        if (nb >= 32) {
-            out[words++] = __builtin_bswap32((uint32_t)(acc >> 32));
-            acc <<= 32;
-            nb -= 32;
-        }
-    }
-    __device__ __forceinline__ void run(uint32_t bit, uint32_t count)
-    {
-        const uint32_t v = bit ? 0xFFFFFFFFu : 0u;
-        for (; count >= 32; count -= 32) bits(v, 32);
-        if (count) bits(v, count);
-    }
+    __device__ __forceinline__ void operator()(uint32_t i, uint32_t word) const { out[i] = word; }
 };
+using LaneBits = BitWriter<uint32_t, OwnStore>;
 
 template <bool PRIOR>
 __global__ __launch_bounds__(kLW) void cbaac_lane_encode_kernel(const uint8_t *__restrict__ sym, int64_t n,
@@ -825,8 +769,7 @@ __global__ __launch_bounds__(kLW) void cbaac_lane_encode_kernel(const uint8_t *_
     uint32_t total;
     lane_model_init(L, PRIOR ? class_prior(prior, act ? seg : 0, nseg, fr.nclass) : nullptr, lane, total);
     double inv = rcp_nr((double)total);
-    LaneBits w;
-    w.out = slots + (act ? seg : 0) * slot_words;
+    LaneBits w{{slots + (act ? seg : 0) * slot_words}};
     uint32_t low = 0, high = 0xFFFFFFFFu, pending = 0;
     const uint8_t *src = sym + start;
     const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
@@ -886,29 +829,9 @@ __global__ __launch_bounds__(kLW) void cbaac_lane_encode_kernel(const uint8_t *_
                 L.E[b][1][lane] = add4(e1, mj1);
                 L.C[0][lane] = add4(c0, mb0);
                 L.C[1][lane] = add4(c1, mb1);
-                // the A8 interval update (the wave kernel's Encoder::code, per lane)
-                const double rng = (double)(high - low) + 1.0, tot = (double)tot_i;
-                const double qh = floordiv(rng * (double)hi_cur, tot, inv);
-                const double ql = floordiv(rng * (double)lo_cur, tot, inv);
-                high = low + (uint32_t)(qh - 1.0);
-                low = low + (uint32_t)ql;
-                const uint32_t d = __builtin_clz(low ^ high);
-                if (d) {
-                    const uint32_t bit = low >> 31;
-                    w.bits(low, 1);
-                    w.run(bit ^ 1u, pending);
-                    pending = 0;
-                    if (d > 1) w.bits(low << 1, d - 1);
-                    low <<= d;
-                    high = (high << d) | ((1u << d) - 1u);
-                }
-                const uint32_t x = (low << 1) & ~(high << 1);
-                const uint32_t p = __builtin_clz(~x);
-                if (p) {
-                    pending += p;
-                    low = (low << p) & 0x7FFFFFFFu;
-                    high = (high << p) | ((1u << p) - 1u) | 0x80000000u;
-                }
+                // the A8 step (the wave kernels' Encoder::code, per lane)
+                narrow(low, high, lo_cur, hi_cur, (double)tot_i, inv);
+                encode_renorm(low, high, pending, w);
                 total = tot_i + 1;
                 lo_n += s_n > s ? 1u : 0u;
                 hi_n += s_n >= s ? 1u : 0u;
@@ -926,23 +849,9 @@ __global__ __launch_bounds__(kLW) void cbaac_lane_encode_kernel(const uint8_t *_
         cur = nxt;
     }
     if (act) {
-        const uint32_t bit = low < kQ1 ? 0u : 1u;   // flush (CBAAC.py:130 -> A8)
-        w.bits(bit << 31, 1);
-        w.run(bit ^ 1u, pending + 1);
-        if (w.nb) w.out[w.words] = __builtin_bswap32((uint32_t)(w.acc >> 32));
-        seg_bits[seg] = (int64_t)w.words * 32 + w.nb;
+        encode_flush(w, low, pending);
+        seg_bits[seg] = (int64_t)w.finish();
     }
-}
-
-// floor(a / t) for integers a < 2^47, 1 <= t <= 2^32 held exactly in doubles,
-// inv ~= 1/t: the quotient estimate is within one of the floor, the remainder
-// (an exact fma) says which way
-__device__ __forceinline__ double floordiv_big(double a, double t, double inv)
-{
-    double q = __builtin_trunc(a * inv);
-    const double r = __builtin_fma(-q, t, a);
-    q = r < 0.0 ? q - 1.0 : (r >= t ? q + 1.0 : q);
-    return q;
 }
 
 // the 16 u16 entries of (a, b): how many are <= v (entries start at 0 and
@@ -1014,8 +923,6 @@ __global__ __launch_bounds__(kLW) void cbaac_lane_decode_kernel(const uint8_t *_
     const int64_t len = act ? (n - start < seg_len ? n - start : seg_len) : 0;
     uint32_t total;
     lane_model_init(L, PRIOR ? class_prior(prior, act ? seg : 0, nseg, fr.nclass) : nullptr, lane, total);
-    double tinv = 1.0 / (double)total;   // (unused until the first symbol; recomputed per symbol)
-    (void)tinv;
     LaneReader br;
     br.p = in + (act ? offs[seg] : 0);
     br.nbytes = act ? offs[seg + 1] - offs[seg] : 0;
@@ -1044,24 +951,8 @@ __global__ __launch_bounds__(kLW) void cbaac_lane_decode_kernel(const uint8_t *_
                 const uint32_t j = nj - 1;
                 const uint32_t lo = cb + elo, hi = cb + ehi;
                 const uint4 mj0 = L.M[j][0], mj1 = L.M[j][1];
-                const double inv = rcp_nr(tot);
-                const double qh = floordiv(rng * (double)hi, tot, inv);
-                const double ql = floordiv(rng * (double)lo, tot, inv);
-                high = low + (uint32_t)(qh - 1.0);
-                low = low + (uint32_t)ql;
-                const uint32_t d = __builtin_clz(low ^ high);
-                if (d) {
-                    low <<= d;
-                    high = (high << d) | ((1u << d) - 1u);
-                    value = (value << d) | br.get(d);
-                }
-                const uint32_t x = (low << 1) & ~(high << 1);
-                const uint32_t p = __builtin_clz(~x);
-                if (p) {
-                    low = (low << p) & 0x7FFFFFFFu;
-                    high = (high << p) | ((1u << p) - 1u) | 0x80000000u;
-                    value = ((value << p) ^ 0x80000000u) | br.get(p);
-                }
+                narrow(low, high, lo, hi, tot, rcp_nr(tot));
+                decode_renorm(low, high, value, br);
                 L.E[b][0][lane] = add4(e0, mj0);
                 L.E[b][1][lane] = add4(e1, mj1);
                 c0 = add4(c0, mb0);
@@ -1109,6 +1000,40 @@ int check_args(int64_t n, int32_t order, int64_t seg_len)
     if (order < 0) return set_error(VCF_ERR_INVALID, "negative order");
     if (order > 1) return set_error(VCF_ERR_UNSUPPORTED, "tiled CBAAC on the GPU: orders 0 and 1 (got %d)", order);
     return VCF_OK;
+}
+
+int check_frames(int64_t n_frames)
+{
+    if (n_frames < 1 || n_frames > 65535) return set_error(VCF_ERR_INVALID, "n_frames %lld (1 .. 65535)", (long long)n_frames);
+    return VCF_OK;
+}
+
+int check_prior_aligned(const void *prior, const char *name)   // the kernels read four frequencies at a time
+{
+    if (reinterpret_cast<uintptr_t>(prior) & 7) return set_error(VCF_ERR_INVALID, "%s not 8-byte aligned", name);
+    return VCF_OK;
+}
+
+// The workspace of an encode call over `groups` groups (the frames of a batch;
+// a plane list is one group) of n units (segments or tiles) each, sw words per
+// slot: the slots, then every unit's bit count, then n + 1 byte offsets per group.
+struct EncodeWs {
+    uint32_t *slots;
+    int64_t *bits, *offs;
+    EncodeWs(void *ws, int64_t groups, int64_t n, int64_t sw)
+        : slots((uint32_t *)ws), bits((int64_t *)(slots + groups * n * sw)), offs(bits + groups * n) {}
+    static int64_t bytes(int64_t groups, int64_t n, int64_t sw) { return groups * (n * sw * 4 + n * 8 + (n + 1) * 8); }
+};
+
+// after an encode kernel: sizes and offsets, then (out_dev given) the bytes packed, group f's at out_dev + f * capacity
+int scan_and_pack(const EncodeWs &w, int64_t groups, int64_t n, int64_t sw, uint8_t *out_dev, int64_t capacity,
+                  int64_t *unit_bytes_dev, hipStream_t st)
+{
+    cbaac_tiled_scan_kernel<<<(unsigned)groups, 1024, 0, st>>>(w.bits, n, w.offs, unit_bytes_dev);
+    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_scan_kernel")) return s;
+    if (!out_dev) return VCF_OK;
+    cbaac_tiled_pack_kernel<<<dim3((unsigned)n, (unsigned)groups), 256, 0, st>>>(w.slots, sw, w.offs, out_dev, capacity);
+    return hip_check(hipGetLastError(), "cbaac_tiled_pack_kernel");
 }
 
 // ---- container version 4: tiles with a two-dimensional context ---------------------
@@ -1208,8 +1133,7 @@ __device__ __forceinline__ void cbaac2d_encode_tile(Lds2d &L, const uint8_t *__r
     lds2d_init(L, rows, lane, m);
     uint32_t ctx = 0;
 
-    BitWriter w;
-    w.out = slot;
+    WaveBits w{{slot, lane}};
     Encoder e;
     for (int32_t y = 0; y < tl.h; ++y) {
         uint8_t *cur = L.row[y & 1];
@@ -1233,14 +1157,14 @@ __device__ __forceinline__ void cbaac2d_encode_tile(Lds2d &L, const uint8_t *__r
                 const uint32_t tot = m.total;
                 uint32_t lo, hi;
                 model_range(m, s, lo, hi);
-                e.code(lo, hi, (double)tot, rcp_exact(tot), w, lane);
+                e.code(lo, hi, (double)tot, rcp_nr((double)tot), w);
                 model_update(m, s, lane);
                 wn = mag3(s);
             }
         }
     }
-    e.flush(w, lane);
-    const uint64_t bits = w.finish(lane);
+    e.flush(w);
+    const uint64_t bits = w.finish();
     if (lane == 0) *bits_out = (int64_t)bits;
 }
 
@@ -1306,45 +1230,6 @@ __global__ __launch_bounds__(64) void cbaac2d_encode_planes_kernel(const uint8_t
                         slots + t * slot_words, tile_bits + t);
 }
 
-// one symbol of the A8 decoder with model m (the body of cbaac_tiled_decode_kernel's loop)
-__device__ __forceinline__ uint32_t decode_step(Model &m, BitReader &br, uint32_t &low, uint32_t &high,
-                                                uint32_t &value, uint32_t lane)
-{
-    const double tot = (double)m.total;
-    const double inv = rcp_nr(tot);
-    const uint32_t span = high - low;
-    const double rng = (double)span + 1.0;
-    const uint32_t T = value - low;
-    const uint32_t f0 = (uint32_t)floordiv(rng * (double)(m.p0 & 0xFFFFu), tot, inv);
-    const uint32_t f1 = (uint32_t)floordiv(rng * (double)(m.p0 >> 16), tot, inv);
-    const uint32_t f2 = (uint32_t)floordiv(rng * (double)(m.p1 & 0xFFFFu), tot, inv);
-    const uint32_t f3 = (uint32_t)floordiv(rng * (double)(m.p1 >> 16), tot, inv);
-    const uint32_t Ln = (uint32_t)__popcll(__ballot(f0 <= T)) - 1;
-    const uint32_t g0 = rl(f0, Ln), g1 = rl(f1, Ln), g2 = rl(f2, Ln), g3 = rl(f3, Ln);
-    const uint32_t g4m1 = Ln == 63 ? span : rl(f0, (Ln + 1) & 63) - 1;
-    const uint32_t j = (T >= g1 ? 1u : 0u) + (T >= g2 ? 1u : 0u) + (T >= g3 ? 1u : 0u);
-    const uint32_t s = 4 * Ln + j;
-    const uint32_t ql = j == 0 ? g0 : j == 1 ? g1 : j == 2 ? g2 : g3;
-    const uint32_t qhm1 = j == 0 ? g1 - 1 : j == 1 ? g2 - 1 : j == 2 ? g3 - 1 : g4m1;
-    high = low + qhm1;
-    low = low + ql;
-    const uint32_t d = __builtin_clz(low ^ high);
-    if (d) {
-        low <<= d;
-        high = (high << d) | ((1u << d) - 1u);
-        value = (value << d) | br.get(d, lane);
-    }
-    const uint32_t x = (low << 1) & ~(high << 1);
-    const uint32_t p = __builtin_clz(~x);
-    if (p) {
-        low = (low << p) & 0x7FFFFFFFu;
-        high = (high << p) | ((1u << p) - 1u) | 0x80000000u;
-        value = ((value << p) ^ 0x80000000u) | br.get(p, lane);
-    }
-    model_update(m, s, lane);
-    return s;
-}
-
 // one tile: `nbytes` of bit stream at `bits` -> its symbols to dst (the tile's first symbol)
 __device__ __forceinline__ void cbaac2d_decode_tile(Lds2d &L, const uint8_t *__restrict__ bits, int64_t nbytes,
                                                     uint8_t *__restrict__ dst, int64_t rs, int64_t C, const Tile2d &tl,
@@ -1355,9 +1240,7 @@ __device__ __forceinline__ void cbaac2d_decode_tile(Lds2d &L, const uint8_t *__r
     lds2d_init(L, rows, lane, m);
     uint32_t ctx = 0;
 
-    BitReader br;
-    br.src = bits;
-    br.nbytes = nbytes;
+    BitReader br{bits, nbytes};
     br.start(lane);
     uint32_t low = 0, high = 0xFFFFFFFFu, value = br.get(32, lane);
     for (int32_t y = 0; y < tl.h; ++y) {
@@ -1462,6 +1345,24 @@ __global__ __launch_bounds__(256) void cbaac2d_hist_planes_kernel(const uint8_t 
 // words per tile slot, even: the int64 tables behind the slots stay 8-byte aligned
 int64_t slot_words_2d(int64_t tile_symbols) { return (slot_words_for(tile_symbols) + 1) & ~(int64_t)1; }
 
+int check_classes(int32_t nclass, const void *priors_dev)
+{
+    if (nclass < 1 || nclass > kMaxClasses) return set_error(VCF_ERR_INVALID, "nclass %d (1 .. %d)", nclass, kMaxClasses);
+    return check_prior_aligned(priors_dev, "priors_dev");
+}
+
+// `rows` histograms: cleared, filled by the caller's kernel, then each made a prior row by its own count
+int clear_hist(uint32_t *hist_dev, int64_t rows, hipStream_t st)
+{
+    return hip_check(hipMemsetAsync(hist_dev, 0, 256 * sizeof(uint32_t) * rows, st), "hipMemsetAsync");
+}
+
+int prior_rows(const uint32_t *hist_dev, int64_t rows, uint16_t *priors_dev, hipStream_t st)
+{
+    cbaac_prior_classes_kernel<<<(unsigned)rows, 256, 0, st>>>(hist_dev, priors_dev);
+    return hip_check(hipGetLastError(), "cbaac_prior_classes_kernel");
+}
+
 int check_2d(int64_t n_frames, int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw, int32_t nclass,
              const void *priors_dev, Geom2d &g)
 {
@@ -1472,10 +1373,8 @@ int check_2d(int64_t n_frames, int64_t H, int64_t W, int64_t C, int64_t th, int6
     if (tw > kMaxTw || th * tw > kMaxTile || th > kMaxTile)
         return set_error(VCF_ERR_UNSUPPORTED, "tiled CBAAC 2-D on the GPU: tiles up to %d wide and %lld symbols", kMaxTw,
                          (long long)kMaxTile);
-    if (n_frames < 1 || n_frames > 65535) return set_error(VCF_ERR_INVALID, "n_frames %lld (1 .. 65535)", (long long)n_frames);
-    if (nclass < 1 || nclass > kMaxClasses) return set_error(VCF_ERR_INVALID, "nclass %d (1 .. %d)", nclass, kMaxClasses);
-    if (priors_dev && (reinterpret_cast<uintptr_t>(priors_dev) & 7))
-        return set_error(VCF_ERR_INVALID, "priors_dev not 8-byte aligned");
+    if (int s = check_frames(n_frames)) return s;
+    if (int s = check_classes(nclass, priors_dev)) return s;
     g = {H, W, C, th, tw, (H + th - 1) / th, (W + tw - 1) / tw};
     if (C * g.ty * g.tx > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many tiles");
     return VCF_OK;
@@ -1505,8 +1404,7 @@ int64_t vcf_cbaac_tiled_workspace(int64_t n, int64_t seg_len)
 {
     const int64_t ns = vcf_cbaac_tiled_segments(n, seg_len);
     if (ns == 0) return 0;
-    // slots, per-segment bit counts, byte offsets (ns + 1)
-    return ns * slot_words_for(seg_len) * 4 + ns * 8 + (ns + 1) * 8;
+    return EncodeWs::bytes(1, ns, slot_words_for(seg_len));
 }
 
 int64_t vcf_cbaac_tiled_bound(int64_t n, int64_t seg_len)
@@ -1533,7 +1431,7 @@ static int tiled_encode(const uint8_t *sym_dev, int64_t n_frames, int64_t n, int
                         int64_t prior_stride = 0, int32_t nclass = 1)
 {
     if (int s = check_args(n, order, seg_len)) return s;
-    if (n_frames < 1 || n_frames > 65535) return set_error(VCF_ERR_INVALID, "n_frames %lld (1 .. 65535)", (long long)n_frames);
+    if (int s = check_frames(n_frames)) return s;
     const int64_t ns = vcf_cbaac_tiled_segments(n, seg_len);
     if (!seg_bytes_dev) return set_error(VCF_ERR_INVALID, "null seg_bytes");
     hipStream_t st = (hipStream_t)stream;
@@ -1541,9 +1439,7 @@ static int tiled_encode(const uint8_t *sym_dev, int64_t n_frames, int64_t n, int
     if (!sym_dev || !ws_dev || (!trace_dev && !out_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
     if (ns > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many segments");
     const int64_t sw = slot_words_for(seg_len);
-    uint32_t *slots = (uint32_t *)ws_dev;
-    int64_t *bits = (int64_t *)(slots + n_frames * ns * sw);
-    int64_t *offs = bits + n_frames * ns;
+    const EncodeWs ws(ws_dev, n_frames, ns, sw);
     Frames fr;
     fr.sym_stride = sym_stride;
     fr.prior_stride = prior_stride;
@@ -1551,24 +1447,18 @@ static int tiled_encode(const uint8_t *sym_dev, int64_t n_frames, int64_t n, int
     const dim3 grid((unsigned)ns, (unsigned)n_frames);
     if (!trace_dev && use_lanes(order, ns * n_frames, false)) {   // one lane per segment
         const dim3 lg((unsigned)((ns + kLW - 1) / kLW), (unsigned)n_frames);
-        if (prior_dev) cbaac_lane_encode_kernel<true><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, slots, sw, bits, prior_dev, fr);
-        else cbaac_lane_encode_kernel<false><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, slots, sw, bits, nullptr, fr);
+        if (prior_dev) cbaac_lane_encode_kernel<true><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, ws.slots, sw, ws.bits, prior_dev, fr);
+        else cbaac_lane_encode_kernel<false><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, ws.slots, sw, ws.bits, nullptr, fr);
     } else if (trace_dev) {
         if (n_frames != 1) return set_error(VCF_ERR_INVALID, "traces take one frame");
-        if (order == 0) cbaac_tiled_encode_kernel<0, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, slots, sw, bits, trace_dev, prior_dev, fr);
-        else cbaac_tiled_encode_kernel<1, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, slots, sw, bits, trace_dev, prior_dev, fr);
+        if (order == 0) cbaac_tiled_encode_kernel<0, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, trace_dev, prior_dev, fr);
+        else cbaac_tiled_encode_kernel<1, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, trace_dev, prior_dev, fr);
     } else {
-        if (order == 0) cbaac_tiled_encode_kernel<0, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, slots, sw, bits, nullptr, prior_dev, fr);
-        else cbaac_tiled_encode_kernel<1, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, slots, sw, bits, nullptr, prior_dev, fr);
+        if (order == 0) cbaac_tiled_encode_kernel<0, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, nullptr, prior_dev, fr);
+        else cbaac_tiled_encode_kernel<1, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, nullptr, prior_dev, fr);
     }
     if (int s = hip_check(hipGetLastError(), "cbaac_tiled_encode_kernel")) return s;
-    cbaac_tiled_scan_kernel<<<(unsigned)n_frames, 1024, 0, st>>>(bits, ns, offs, seg_bytes_dev);
-    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_scan_kernel")) return s;
-    if (out_dev) {
-        cbaac_tiled_pack_kernel<<<grid, 256, 0, st>>>(slots, sw, offs, out_dev, out_capacity);
-        if (int s = hip_check(hipGetLastError(), "cbaac_tiled_pack_kernel")) return s;
-    }
-    return VCF_OK;
+    return scan_and_pack(ws, n_frames, ns, sw, out_dev, out_capacity, seg_bytes_dev, st);
 }
 
 int vcf_cbaac_tiled_encode(const uint8_t *sym_dev, int64_t n, int32_t order, int64_t seg_len, uint8_t *out_dev,
@@ -1592,7 +1482,7 @@ static int tiled_decode(const uint8_t *in_dev, const int64_t *seg_offsets_dev, i
                         const uint16_t *prior_dev, int64_t prior_stride, int32_t nclass = 1)
 {
     if (int s = check_args(n, order, seg_len)) return s;
-    if (n_frames < 1 || n_frames > 65535) return set_error(VCF_ERR_INVALID, "n_frames %lld (1 .. 65535)", (long long)n_frames);
+    if (int s = check_frames(n_frames)) return s;
     const int64_t ns = vcf_cbaac_tiled_segments(n, seg_len);
     if (ns == 0) return VCF_OK;
     if (!in_dev || !seg_offsets_dev || !sym_dev) return set_error(VCF_ERR_INVALID, "null buffer");
@@ -1626,12 +1516,11 @@ static int tiled_prior(const uint8_t *sym_dev, int64_t n_frames, int64_t n, int6
                        uint32_t *hist_dev, void *stream)
 {
     if (n < 0) return set_error(VCF_ERR_INVALID, "negative symbol count");
-    if (n_frames < 1 || n_frames > 65535) return set_error(VCF_ERR_INVALID, "n_frames %lld (1 .. 65535)", (long long)n_frames);
+    if (int s = check_frames(n_frames)) return s;
     if (!prior_dev || !hist_dev || (n > 0 && !sym_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
-    if (reinterpret_cast<uintptr_t>(prior_dev) & 7) return set_error(VCF_ERR_INVALID, "prior_dev not 8-byte aligned");
+    if (int s = check_prior_aligned(prior_dev, "prior_dev")) return s;
     hipStream_t st = (hipStream_t)stream;
-    if (int s = hip_check(hipMemsetAsync(hist_dev, 0, 256 * sizeof(uint32_t) * n_frames, st), "hipMemsetAsync"))
-        return s;
+    if (int s = clear_hist(hist_dev, n_frames, st)) return s;
     if (n > 0) {
         const int64_t blocks = std::min<int64_t>((n + 4095) / 4096, 2048);
         cbaac_hist_kernel<<<dim3((unsigned)blocks, (unsigned)n_frames), 256, 0, st>>>(sym_dev, n, hist_dev, sym_stride);
@@ -1652,7 +1541,7 @@ int vcf_cbaac_tiled_encode_prior(const uint8_t *sym_dev, int64_t n, int32_t orde
 {
     if (out_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
     if (n > 0 && (!out_dev || !prior_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
-    if (reinterpret_cast<uintptr_t>(prior_dev) & 7) return set_error(VCF_ERR_INVALID, "prior_dev not 8-byte aligned");
+    if (int s = check_prior_aligned(prior_dev, "prior_dev")) return s;
     return tiled_encode(sym_dev, 1, n, 0, order, seg_len, out_dev, out_capacity, seg_bytes_dev, nullptr, ws_dev, stream,
                         prior_dev);
 }
@@ -1661,7 +1550,7 @@ int vcf_cbaac_tiled_decode_prior(const uint8_t *in_dev, const int64_t *seg_offse
                                  const uint16_t *prior_dev, int64_t seg_len, uint8_t *sym_dev, void *stream)
 {
     if (n > 0 && !prior_dev) return set_error(VCF_ERR_INVALID, "null prior");
-    if (reinterpret_cast<uintptr_t>(prior_dev) & 7) return set_error(VCF_ERR_INVALID, "prior_dev not 8-byte aligned");
+    if (int s = check_prior_aligned(prior_dev, "prior_dev")) return s;
     return tiled_decode(in_dev, seg_offsets_dev, 1, n, order, seg_len, sym_dev, 0, stream, prior_dev, 0);
 }
 
@@ -1679,8 +1568,7 @@ int vcf_cbaac_tiled_encode_frames(const uint8_t *sym_dev, int64_t n_frames, int6
 {
     if (out_frame_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
     if (frame_symbols > 0 && !out_dev) return set_error(VCF_ERR_INVALID, "null output buffer");
-    if (priors_dev && (reinterpret_cast<uintptr_t>(priors_dev) & 7))
-        return set_error(VCF_ERR_INVALID, "priors_dev not 8-byte aligned");
+    if (int s = check_prior_aligned(priors_dev, "priors_dev")) return s;
     return tiled_encode(sym_dev, n_frames, frame_symbols, frame_stride, order, seg_len, out_dev, out_frame_capacity,
                         seg_bytes_dev, nullptr, ws_dev, stream, priors_dev, priors_dev ? 256 : 0);
 }
@@ -1689,32 +1577,23 @@ int vcf_cbaac_tiled_decode_frames(const uint8_t *in_dev, const int64_t *seg_offs
                                   int64_t frame_symbols, int32_t order, const uint16_t *priors_dev, int64_t seg_len,
                                   uint8_t *sym_dev, int64_t out_frame_stride, void *stream)
 {
-    if (priors_dev && (reinterpret_cast<uintptr_t>(priors_dev) & 7))
-        return set_error(VCF_ERR_INVALID, "priors_dev not 8-byte aligned");
+    if (int s = check_prior_aligned(priors_dev, "priors_dev")) return s;
     return tiled_decode(in_dev, seg_offsets_dev, n_frames, frame_symbols, order, seg_len, sym_dev, out_frame_stride,
                         stream, priors_dev, priors_dev ? 256 : 0);
 }
 
 // ---- version 3: prior classes (consecutive runs of segments share a prior row) ----
-static int check_classes(int32_t nclass, const void *priors_dev)
-{
-    if (nclass < 1 || nclass > kMaxClasses) return set_error(VCF_ERR_INVALID, "nclass %d (1 .. %d)", nclass, kMaxClasses);
-    if (priors_dev && (reinterpret_cast<uintptr_t>(priors_dev) & 7))
-        return set_error(VCF_ERR_INVALID, "priors_dev not 8-byte aligned");
-    return VCF_OK;
-}
-
 int vcf_cbaac_tiled_prior_classes(const uint8_t *sym_dev, int64_t n_frames, int64_t frame_symbols,
                                   int64_t frame_stride, int64_t seg_len, int32_t nclass, uint16_t *priors_dev,
                                   uint32_t *hist_dev, void *stream)
 {
     if (int s = check_args(frame_symbols, 0, seg_len)) return s;
     if (int s = check_classes(nclass, priors_dev)) return s;
-    if (n_frames < 1 || n_frames > 65535) return set_error(VCF_ERR_INVALID, "n_frames %lld (1 .. 65535)", (long long)n_frames);
+    if (int s = check_frames(n_frames)) return s;
     if (!priors_dev || !hist_dev || (frame_symbols > 0 && !sym_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows = n_frames * nclass;
-    if (int s = hip_check(hipMemsetAsync(hist_dev, 0, 256 * sizeof(uint32_t) * rows, st), "hipMemsetAsync")) return s;
+    if (int s = clear_hist(hist_dev, rows, st)) return s;
     const int64_t ns = vcf_cbaac_tiled_segments(frame_symbols, seg_len);
     if (ns > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many segments");
     if (ns > 0) {
@@ -1722,8 +1601,7 @@ int vcf_cbaac_tiled_prior_classes(const uint8_t *sym_dev, int64_t n_frames, int6
                                                                                           nclass, hist_dev, frame_stride);
         if (int s = hip_check(hipGetLastError(), "cbaac_hist_classes_kernel")) return s;
     }
-    cbaac_prior_classes_kernel<<<(unsigned)rows, 256, 0, st>>>(hist_dev, priors_dev);
-    return hip_check(hipGetLastError(), "cbaac_prior_classes_kernel");
+    return prior_rows(hist_dev, rows, priors_dev, st);
 }
 
 int vcf_cbaac_tiled_encode_classes(const uint8_t *sym_dev, int64_t n_frames, int64_t frame_symbols,
@@ -1759,8 +1637,7 @@ int64_t vcf_cbaac_tiled2d_workspace(int64_t n_frames, int64_t H, int64_t W, int6
 {
     const int64_t nt = vcf_cbaac_tiled2d_tiles(H, W, C, th, tw);
     if (nt == 0 || n_frames <= 0) return 0;
-    // slots, per-tile bit counts, byte offsets (nt + 1), per frame
-    return n_frames * (nt * slot_words_2d(th * tw) * 4 + nt * 8 + (nt + 1) * 8);
+    return EncodeWs::bytes(n_frames, nt, slot_words_2d(th * tw));
 }
 
 int64_t vcf_cbaac_tiled2d_bound(int64_t H, int64_t W, int64_t C, int64_t th, int64_t tw)
@@ -1779,14 +1656,13 @@ int vcf_cbaac_tiled2d_prior_frames(const uint8_t *sym_dev, int64_t n_frames, int
     if (!priors_dev || !hist_dev || (nt > 0 && !sym_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows = n_frames * nclass * kCtx2d;
-    if (int s = hip_check(hipMemsetAsync(hist_dev, 0, 256 * sizeof(uint32_t) * rows, st), "hipMemsetAsync")) return s;
+    if (int s = clear_hist(hist_dev, rows, st)) return s;
     if (nt > 0) {
         cbaac2d_hist_kernel<<<dim3((unsigned)nt, (unsigned)n_frames), 256, 0, st>>>(sym_dev, g, nclass, hist_dev,
                                                                                    frame_stride);
         if (int s = hip_check(hipGetLastError(), "cbaac2d_hist_kernel")) return s;
     }
-    cbaac_prior_classes_kernel<<<(unsigned)rows, 256, 0, st>>>(hist_dev, priors_dev);
-    return hip_check(hipGetLastError(), "cbaac_prior_classes_kernel");
+    return prior_rows(hist_dev, rows, priors_dev, st);
 }
 
 int vcf_cbaac_tiled2d_encode_frames(const uint8_t *sym_dev, int64_t n_frames, int64_t H, int64_t W, int64_t C,
@@ -1803,20 +1679,15 @@ int vcf_cbaac_tiled2d_encode_frames(const uint8_t *sym_dev, int64_t n_frames, in
     if (nt == 0) return hip_check(hipMemsetAsync(tile_bytes_dev, 0, 8 * n_frames, st), "hipMemsetAsync");
     if (!sym_dev || !ws_dev || !out_dev || !priors_dev) return set_error(VCF_ERR_INVALID, "null buffer");
     const int64_t sw = slot_words_2d(th * tw);
-    uint32_t *slots = (uint32_t *)ws_dev;
-    int64_t *bits = (int64_t *)(slots + n_frames * nt * sw);
-    int64_t *offs = bits + n_frames * nt;
+    const EncodeWs ws(ws_dev, n_frames, nt, sw);
     Frames fr;
     fr.sym_stride = frame_stride;
     fr.prior_stride = 256LL * kCtx2d * nclass;
     fr.nclass = nclass;
-    const dim3 grid((unsigned)nt, (unsigned)n_frames);
-    cbaac2d_encode_kernel<<<grid, 64, 0, st>>>(sym_dev, g, slots, sw, bits, priors_dev, fr);
+    cbaac2d_encode_kernel<<<dim3((unsigned)nt, (unsigned)n_frames), 64, 0, st>>>(sym_dev, g, ws.slots, sw, ws.bits,
+                                                                               priors_dev, fr);
     if (int s = hip_check(hipGetLastError(), "cbaac2d_encode_kernel")) return s;
-    cbaac_tiled_scan_kernel<<<(unsigned)n_frames, 1024, 0, st>>>(bits, nt, offs, tile_bytes_dev);
-    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_scan_kernel")) return s;
-    cbaac_tiled_pack_kernel<<<grid, 256, 0, st>>>(slots, sw, offs, out_dev, out_frame_capacity);
-    return hip_check(hipGetLastError(), "cbaac_tiled_pack_kernel");
+    return scan_and_pack(ws, n_frames, nt, sw, out_dev, out_frame_capacity, tile_bytes_dev, st);
 }
 
 int vcf_cbaac_tiled2d_decode_frames(const uint8_t *in_dev, const int64_t *tile_offsets_dev, int64_t n_frames, int64_t H,
@@ -1867,8 +1738,7 @@ static int check_planes(const vcf_plane_desc *desc_host, const void *desc_dev, i
 int64_t vcf_cbaac_tiled2d_planes_workspace(int64_t n_tiles, int64_t th, int64_t tw)
 {
     if (n_tiles <= 0 || th < 1 || tw < 1) return 0;
-    // slots, per-tile bit counts, byte offsets (n_tiles + 1)
-    return n_tiles * slot_words_2d(th * tw) * 4 + n_tiles * 8 + (n_tiles + 1) * 8;
+    return EncodeWs::bytes(1, n_tiles, slot_words_2d(th * tw));
 }
 
 int64_t vcf_cbaac_tiled2d_planes_bound(int64_t n_tiles, int64_t th, int64_t tw)
@@ -1884,12 +1754,11 @@ int vcf_cbaac_tiled2d_prior_planes(const uint8_t *buf_dev, int64_t buf_bytes, co
     if (!priors_dev || !hist_dev || !buf_dev) return set_error(VCF_ERR_INVALID, "null buffer");
     hipStream_t st = (hipStream_t)stream;
     const int64_t rows = n_arrays * nclass * kCtx2d;
-    if (int s = hip_check(hipMemsetAsync(hist_dev, 0, 256 * sizeof(uint32_t) * rows, st), "hipMemsetAsync")) return s;
+    if (int s = clear_hist(hist_dev, rows, st)) return s;
     cbaac2d_hist_planes_kernel<<<(unsigned)n_tiles, 256, 0, st>>>(buf_dev, desc_dev, (int32_t)n_arrays, th, tw, nclass,
                                                                   hist_dev);
     if (int s = hip_check(hipGetLastError(), "cbaac2d_hist_planes_kernel")) return s;
-    cbaac_prior_classes_kernel<<<(unsigned)rows, 256, 0, st>>>(hist_dev, priors_dev);
-    return hip_check(hipGetLastError(), "cbaac_prior_classes_kernel");
+    return prior_rows(hist_dev, rows, priors_dev, st);
 }
 
 int vcf_cbaac_tiled2d_encode_planes(const uint8_t *buf_dev, int64_t buf_bytes, const vcf_plane_desc *desc_host,
@@ -1903,16 +1772,11 @@ int vcf_cbaac_tiled2d_encode_planes(const uint8_t *buf_dev, int64_t buf_bytes, c
     if (!buf_dev || !ws_dev || !out_dev || !priors_dev || !tile_bytes_dev) return set_error(VCF_ERR_INVALID, "null buffer");
     hipStream_t st = (hipStream_t)stream;
     const int64_t sw = slot_words_2d(th * tw);
-    uint32_t *slots = (uint32_t *)ws_dev;
-    int64_t *bits = (int64_t *)(slots + n_tiles * sw);
-    int64_t *offs = bits + n_tiles;
-    cbaac2d_encode_planes_kernel<<<(unsigned)n_tiles, 64, 0, st>>>(buf_dev, desc_dev, (int32_t)n_arrays, th, tw, slots, sw,
-                                                                   bits, priors_dev, nclass);
+    const EncodeWs ws(ws_dev, 1, n_tiles, sw);
+    cbaac2d_encode_planes_kernel<<<(unsigned)n_tiles, 64, 0, st>>>(buf_dev, desc_dev, (int32_t)n_arrays, th, tw, ws.slots,
+                                                                   sw, ws.bits, priors_dev, nclass);
     if (int s = hip_check(hipGetLastError(), "cbaac2d_encode_planes_kernel")) return s;
-    cbaac_tiled_scan_kernel<<<1, 1024, 0, st>>>(bits, n_tiles, offs, tile_bytes_dev);
-    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_scan_kernel")) return s;
-    cbaac_tiled_pack_kernel<<<(unsigned)n_tiles, 256, 0, st>>>(slots, sw, offs, out_dev, out_capacity);
-    return hip_check(hipGetLastError(), "cbaac_tiled_pack_kernel");
+    return scan_and_pack(ws, 1, n_tiles, sw, out_dev, out_capacity, tile_bytes_dev, st);
 }
 
 int vcf_cbaac_tiled2d_decode_planes(const uint8_t *in_dev, const int64_t *tile_offsets_dev,
