@@ -379,17 +379,14 @@ int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32
  * full-block area the (dx, dy) of the full search (fast = 0,
  * _process_block_row :207-246) or the three-step search (fast = 1,
  * _three_step_search :159-204) over [-sr, sr].  mv_dev: (H/bs) x (W/bs) x 2
- * float32; gray_workspace_dev: 2*H*W bytes.  bs <= 64, sr <= 32. */
+ * float32; gray_workspace_dev: 2*H*W bytes.  bs <= 64, sr <= 32.
+ * Kernels: the full search runs on 4-pixel words (v_alignbyte + v_sad_u8,
+ * one lane per candidate) when bs % 4 == 0 and byte by byte otherwise; the
+ * three-step search runs its 8 neighbours in parallel rounds for bs = 16 and
+ * one candidate at a time otherwise.  Identical motion fields either way
+ * (vcf_ipp_block_match_variant of the A/B library picks per call). */
 int vcf_ipp_block_match(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, int32_t bs,
                         int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream);
-
-/* Block-matching kernel choice (benchmarking and tests; process-wide):
- * 0 = the word kernels -- full search on 4-pixel words (v_alignbyte +
- * v_sad_u8, one lane per candidate) when bs % 4 == 0, and for bs = 16 the
- * three-step search in parallel rounds of its 8 neighbours; 1 = the byte
- * kernels (full search) and the serial three-step kernel.  Both give
- * identical motion fields. */
-int vcf_ipp_set_full_search_variant(int32_t variant);
 
 /* IPP.motion_compensate (IPP_DCT.py:378-395). */
 int vcf_ipp_motion_compensate(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,
@@ -447,9 +444,15 @@ int vcf_cbaac_model_trace(const uint8_t *symbols, int64_t n, int32_t order, int3
  * The flattened symbols split into consecutive segments of seg_len symbols
  * (a multiple of 256); each segment is coded exactly as vcf_cbaac_encode
  * codes it alone: CBAAC.CoDec._encode (CBAAC.py:114-131) with a fresh
- * ContextManager (:49-69) and history per segment, one wave per segment.
+ * ContextManager (:49-69) and history per segment.
  * Orders 0 and 1 (VCF_ERR_UNSUPPORTED above).  Device pointers; the
- * container (segment sizes + payload) is vcf_amd/tcbaac.py's. */
+ * container (segment sizes + payload) is vcf_amd/tcbaac.py's.
+ * Kernels (every vcf_cbaac_tiled_encode* / _decode* below; same bytes): one
+ * segment per wave (64 lanes share one model: a shorter time per segment),
+ * except that order 0 codes one segment per LANE (64 segments per wave, each
+ * with its own model in LDS) once a call has at least 4608 segments to
+ * encode / 6144 to decode, over all frames of the call.  The A/B library's
+ * *_variant twins (include/vcf_amd_ab.h) take the choice per call. */
 int64_t vcf_cbaac_tiled_segments(int64_t n, int64_t seg_len);
 /* scratch bytes (ws_dev) for vcf_cbaac_tiled_encode / _trace */
 int64_t vcf_cbaac_tiled_workspace(int64_t n, int64_t seg_len);
@@ -460,13 +463,6 @@ int64_t vcf_cbaac_tiled_bound(int64_t n, int64_t seg_len);
  * means the output was cut: retry with vcf_cbaac_tiled_bound bytes). */
 int vcf_cbaac_tiled_encode(const uint8_t *sym_dev, int64_t n, int32_t order, int64_t seg_len, uint8_t *out_dev,
                            int64_t out_capacity, int64_t *seg_bytes_dev, void *ws_dev, void *stream);
-/* Kernel choice (process-wide; A/B and tests): 0 = automatic -- order 0 codes
- * one segment per LANE (64 segments per wave, each with its own model in
- * LDS) once a call has at least 4608 segments to encode / 6144 to decode
- * (all frames of the call), else one segment per wave
- * (64 lanes share one model: a shorter time per segment); 1 = one segment per
- * wave always; 2 = one segment per lane for order 0 always.  Same bytes. */
-int vcf_cbaac_tiled_set_variant(int32_t variant);
 /* The model alone: the (low, high, total) triple handed to the coder for
  * every symbol (3*n int32), segment by segment (parity checks). */
 int vcf_cbaac_tiled_trace(const uint8_t *sym_dev, int64_t n, int32_t order, int64_t seg_len, int32_t *triples_dev,

@@ -164,10 +164,8 @@ def ipp(args):
     cpu = {fast: cpu_port(lambda: O.ipp_block_matching(f0, f1, bs, sr, bool(fast)), H * W,
                           "one 4K frame pair, oracle/vcf_ipp_oracle.c")[0] for fast in (0, 1)}
     for fast, kv in ((0, 0), (0, 1), (1, 0), (1, 1)):
-        L.call("vcf_ipp_set_full_search_variant", kv)
-
         def me():
-            L.call("vcf_ipp_block_match", dr.ptr, dc.ptr, H, W, bs, sr, fast, dmv.ptr, dg.ptr, s.handle)
+            L.call_v(kv, "vcf_ipp_block_match", dr.ptr, dc.ptr, H, W, bs, sr, fast, dmv.ptr, dg.ptr, s.handle)
 
         def pframe():
             me()
@@ -176,7 +174,6 @@ def ipp(args):
         t_me = timed(s, me, args.steps, 3)
         t_p = timed(s, pframe, args.steps, 3)
         sads = (H // bs) * (W // bs) * (2 * sr + 1) ** 2 * bs * bs
-        L.call("vcf_ipp_set_full_search_variant", 0)
         print(json.dumps({"metric": f"ipp {'tss' if fast else 'full-search'} motion estimation 4K bs=16 S=8",
                           "variant": ("three-step, " + ("serial kernel" if kv else "parallel rounds")) if fast
                           else ("byte kernel" if kv else "word kernel"),

@@ -88,8 +88,7 @@ def time_gpu():
         # one lane per segment from 4608 segments on
         for name, fb in (("v4", T.FrameBatch2D(F, shape, T.TILE_2D, K)),
                          ("v3", T.FrameBatch(F, n, 0, T.CLASS_SEG, prior=True, nclass=K)),
-                         ("v3_wave", T.FrameBatch(F, n, 0, T.CLASS_SEG, prior=True, nclass=K))):
-            L.call("vcf_cbaac_tiled_set_variant", 1 if name == "v3_wave" else 0)
+                         ("v3_wave", T.FrameBatch(F, n, 0, T.CLASS_SEG, prior=True, nclass=K, kernel=1))):
             enc_ms = timed(lambda: fb.launch(buf), fb.stream, reps)
             got = fb.download()
             payload = b"".join(e[1] for e in got)
@@ -108,13 +107,12 @@ def time_gpu():
                            n, h)
             else:
                 def dec():
-                    L.call("vcf_cbaac_tiled_decode_classes", src.ptr, doffs.ptr, F, n, 0, dpr.ptr, K, T.CLASS_SEG,
-                           out.ptr, n, h)
+                    L.call_v(fb.kernel, "vcf_cbaac_tiled_decode_classes", src.ptr, doffs.ptr, F, n, 0, dpr.ptr, K,
+                             T.CLASS_SEG, out.ptr, n, h)
             dec_ms = timed(dec, fb.stream, reps)
             ok = bool(np.array_equal(out.download(np.empty(F * n, np.uint8)).reshape(F, *shape)[F - 1], k))
             res[name] = dict(encode_ms=round(enc_ms, 3), decode_ms=round(dec_ms, 3), units=fb.ns,
                              payload_bytes_per_frame=len(payload) // F, round_trip=ok)
-        L.call("vcf_cbaac_tiled_set_variant", 0)
         rows.append(dict(case="tcbaac2d_time", frame=[H, W, 3], Q=Q, frames=F, v4=res["v4"], v3=res["v3"],
                          v3_wave=res["v3_wave"],
                          encode_v4_over_v3_wave=round(res["v4"]["encode_ms"] / res["v3_wave"]["encode_ms"], 3),

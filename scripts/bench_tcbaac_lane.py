@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Tiled CBAAC kernel timing, one segment per wave (variant 1) vs one per
-lane (variant 2), order 0, prior-seeded (-c TCBAACP): one 1080p frame, and
+"""Tiled CBAAC kernel timing, one segment per wave (kernel 1) vs one per
+lane (kernel 2), order 0, prior-seeded (-c TCBAACP): one 1080p frame, and
 batches of 1080p frames coded in one launch (throughput).  One JSON line each.
 usage: bench_tcbaac_lane.py [frames,frames,...] [seg_len,...]"""
 import json
@@ -41,10 +41,9 @@ def main():
 
     for seg_len in seg_lens:
         for variant in (1, 2):
-            L.call("vcf_cbaac_tiled_set_variant", variant)
             for name, sym, reps in cases:
                 n = sym.size
-                coder = T.TiledCoder(0, seg_len, stream=st, prior=True)
+                coder = T.TiledCoder(0, seg_len, stream=st, prior=True, kernel=variant)
                 sizes, payload = coder.encode(sym)
                 prior = coder.last_prior
                 dsym = DeviceBuffer.from_array(sym, st)
@@ -52,13 +51,13 @@ def main():
                 cap = int(lib.vcf_cbaac_tiled_bound(n, seg_len))
                 out, sb = DeviceBuffer(cap), DeviceBuffer(8 * (len(sizes) + 1))
                 pr = DeviceBuffer.from_array(prior, st)
-                enc = timed(lambda: L.call("vcf_cbaac_tiled_encode_prior", dsym.ptr, n, 0, pr.ptr, seg_len, out.ptr,
-                                           cap, sb.ptr, ws.ptr, st.handle), reps)
+                enc = timed(lambda: L.call_v(variant, "vcf_cbaac_tiled_encode_prior", dsym.ptr, n, 0, pr.ptr, seg_len,
+                                             out.ptr, cap, sb.ptr, ws.ptr, st.handle), reps)
                 offs = DeviceBuffer.from_array(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64), st)
                 src = DeviceBuffer.from_array(np.frombuffer(payload, np.uint8), st)
                 dec_out = DeviceBuffer(n)
-                dec = timed(lambda: L.call("vcf_cbaac_tiled_decode_prior", src.ptr, offs.ptr, n, 0, pr.ptr, seg_len,
-                                           dec_out.ptr, st.handle), reps)
+                dec = timed(lambda: L.call_v(variant, "vcf_cbaac_tiled_decode_prior", src.ptr, offs.ptr, n, 0, pr.ptr,
+                                             seg_len, dec_out.ptr, st.handle), reps)
                 back = np.empty(n, np.uint8)
                 dec_out.download(back)
                 print(json.dumps(dict(case="tcbaacp", variant=["auto", "wave", "lane"][variant], frames=name, seg_len=seg_len,
@@ -66,7 +65,6 @@ def main():
                                       encode_ms=round(enc, 3), decode_ms=round(dec, 3),
                                       encode_Gsym_s=round(n / enc / 1e6, 3), decode_Gsym_s=round(n / dec / 1e6, 3),
                                       round_trip=bool(np.array_equal(back, sym)))), flush=True)
-    L.call("vcf_cbaac_tiled_set_variant", 0)
 
 
 if __name__ == "__main__":

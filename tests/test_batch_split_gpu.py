@@ -266,23 +266,26 @@ def test_cbaac_batch_limit_and_largest_batch(kind, variant):
              sizes=DeviceBuffer(8 * (parts + 1) * over), dec=DeviceBuffer(stride * over))
     b["dec"].fill(0xA5)
     b["out"].fill(0)
+
+    def run(entry, args):                                   # a variant: the coders' twins (a prior has one kernel)
+        if variant and "_prior_" not in entry:
+            return L.call_ab(entry + "_variant", variant, *args)
+        return L.call(entry, *args)
     try:
-        L.call("vcf_cbaac_tiled_set_variant", variant)
-        for entry, args in _cbaac_calls(kind, over, b, stride):
+        for stage in _cbaac_calls(kind, over, b, stride):
             with pytest.raises(L.VCFInvalidArgument, match="n_frames 65536"):
-                L.call(entry, *args)
+                run(*stage)
         prior_stage, encode_stage, decode_stage = _cbaac_calls(kind, F, b, stride)
-        L.call(prior_stage[0], *prior_stage[1])
+        run(*prior_stage)
         prior = b["prior"].download(np.empty((F,) + ref["prior"].shape[1:], np.uint16))
         assert np.array_equal(prior, S.batch(ref["prior"], F))
         del prior                                           # the device's rows are the host's: the next stages read them
-        L.call(encode_stage[0], *encode_stage[1])
+        run(*encode_stage)
         sizes = b["sizes"].download(np.empty((F, parts + 1), np.int64))
         out = b["out"].download(np.empty((F, cap), np.uint8))
-        L.call(decode_stage[0], *decode_stage[1])
+        run(*decode_stage)
         dec = b["dec"].download(np.empty((F, stride), np.uint8))
     finally:
-        L.call("vcf_cbaac_tiled_set_variant", 0)
         _free(*(v for v in b.values() if isinstance(v, DeviceBuffer)))
     want_sizes = S.batch(ref["sizes"], F)
     assert np.array_equal(sizes[:, :parts], want_sizes) and np.array_equal(sizes[:, parts], want_sizes.sum(axis=1))

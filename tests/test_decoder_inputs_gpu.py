@@ -125,21 +125,16 @@ def test_inflate_window_check_counts_no_violation():
 @pytest.mark.parametrize("order", [0, 1])
 @pytest.mark.parametrize("seg_len", [256, 4096])
 def test_cbaac_decoders_equal_host_on_any_bytes(order, seg_len):
-    from vcf_amd import _lib as L
     from vcf_amd import tcbaac as T
     entries = DI.cbaac_payloads(host_encode, order, seg_len)
     want = [host_decode(e) for e in entries]
-    coder = T.TiledCoder(order, seg_len)
-    try:
-        for variant in (1, 2) if order == 0 else (1,):     # one wave / one lane (order 0) per segment
-            L.call("vcf_cbaac_tiled_set_variant", variant)
-            for e, w in zip(entries, want):
-                kind, _, _, n, prior, seg_bytes, payload, _ = e
-                got = coder.decode(payload, seg_bytes, n, prior)
-                rows = 0 if prior is None else prior.shape[0] if prior.ndim == 2 else 1
-                assert np.array_equal(got, w), (variant, kind, n, rows, np.nonzero(got != w)[0][:5])
-    finally:
-        L.call("vcf_cbaac_tiled_set_variant", 0)
+    for variant in (1, 2) if order == 0 else (1,):     # one wave / one lane (order 0) per segment
+        coder = T.TiledCoder(order, seg_len, kernel=variant)
+        for e, w in zip(entries, want):
+            kind, _, _, n, prior, seg_bytes, payload, _ = e
+            got = coder.decode(payload, seg_bytes, n, prior)
+            rows = 0 if prior is None else prior.shape[0] if prior.ndim == 2 else 1
+            assert np.array_equal(got, w), (variant, kind, n, rows, np.nonzero(got != w)[0][:5])
 
 
 @pytest.mark.parametrize("variant", [1, 2])
@@ -163,13 +158,9 @@ def test_cbaac_batched_decode_on_any_bytes(variant):
     src, doffs, dpr = (DeviceBuffer.from_array(np.frombuffer(b"".join(e[6] for e in entries), np.uint8)),
                        DeviceBuffer.from_array(offs), DeviceBuffer.from_array(priors))
     out = DeviceBuffer.from_array(np.full(F * stride, _FILL, np.uint8))
-    try:
-        L.call("vcf_cbaac_tiled_set_variant", variant)
-        L.call("vcf_cbaac_tiled_decode_classes", src.ptr, doffs.ptr, F, n, 0, dpr.ptr, priors.shape[1], seg, out.ptr,
-               stride, None)
-        got = out.download(np.empty(F * stride, np.uint8)).reshape(F, stride)
-    finally:
-        L.call("vcf_cbaac_tiled_set_variant", 0)
+    L.call_ab("vcf_cbaac_tiled_decode_classes_variant", variant, src.ptr, doffs.ptr, F, n, 0, dpr.ptr, priors.shape[1],
+              seg, out.ptr, stride, None)
+    got = out.download(np.empty(F * stride, np.uint8)).reshape(F, stride)
     for f, e in enumerate(entries):
         assert np.array_equal(got[f, :n], host_decode(e)), e[0]
     assert (got[:, n:] == _FILL).all()          # the bytes between two frames' outputs

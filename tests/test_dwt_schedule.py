@@ -29,10 +29,21 @@ def test_product_sources_read_no_other_environment():
     assert sorted(found) == sorted(GETENV_ALLOWED), found
 
 
-def test_public_header_has_no_dwt_setter():
+def test_public_header_has_no_kernel_setter():
+    """No entry of the product ABI switches a kernel for the process: the declared names with `set`
+    in them are the device, a fill, and the deflate workspace budget (a per-device resource)."""
     src = open(os.path.join(ROOT, "include", "vcf_amd.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    assert not re.findall(r"\bvcf_dwt\w*set\w*\s*\(", src)
+    assert sorted(set(re.findall(r"\b(vcf_\w*set\w*)\s*\(", src))) == ["vcf_memset", "vcf_set_device",
+                                                                      "vcf_zlib_set_workspace_budget"]
+
+
+def test_product_library_exports_no_kernel_setter():
+    """The two process-wide switches it once had (names in two pieces: a search of the tree for them
+    should find callers, not this test)."""
+    import vcf_amd._lib as L
+    for name in ("vcf_cbaac_tiled_set" "_variant", "vcf_ipp_set" "_full_search_variant"):
+        assert not hasattr(L.lib(), name), name
 
 
 @pytest.fixture(scope="module")

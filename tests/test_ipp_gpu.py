@@ -78,11 +78,7 @@ def test_full_search_word_and_byte_kernels_agree(K, bs, sr):
     noisy = rng.integers(0, 256, (120, 200, 3), dtype=np.uint8)
     flat = np.full((120, 200, 3), 40, np.uint8)
     for a, b in ((fr[0], fr[1]), (noisy, fr[1]), (flat, flat), (fr[1], noisy)):
-        try:
-            K.set_full_search_variant(1)
-            want = K.block_matching(a, b, bs, sr, False)
-        finally:
-            K.set_full_search_variant(0)
+        want = K.block_matching(a, b, bs, sr, False, variant=1)
         assert np.array_equal(K.block_matching(a, b, bs, sr, False), want)
 
 
@@ -96,11 +92,7 @@ def test_tss16_parallel_rounds_agree_with_serial_kernel(K, sr):
     noisy = rng.integers(0, 256, (144, 208, 3), dtype=np.uint8)
     flat = np.full((144, 208, 3), 90, np.uint8)
     for a, b in ((fr[0], fr[1]), (noisy, fr[1]), (fr[1], noisy), (flat, flat), (noisy, noisy[::-1].copy())):
-        try:
-            K.set_full_search_variant(1)
-            want = K.block_matching(a, b, 16, sr, True)
-        finally:
-            K.set_full_search_variant(0)
+        want = K.block_matching(a, b, 16, sr, True, variant=1)
         got = K.block_matching(a, b, 16, sr, True)
         assert np.array_equal(got, want)
         assert np.array_equal(got, O.ipp_block_matching(a, b, 16, sr, True))

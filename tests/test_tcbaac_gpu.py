@@ -263,31 +263,82 @@ def test_threaded_encode_fns_decode_fns(tmp_path, codec):
 @pytest.mark.parametrize("prior", [False, True])
 @pytest.mark.parametrize("seg_len", [256, 4096, 32768])
 def test_lane_kernels_equal_wave_kernels(prior, seg_len):
-    """Order 0 codes one segment per lane (vcf_cbaac_tiled_set_variant(2); the
-    default from 2048 segments on) or one per wave (1): identical streams, and
+    """Order 0 codes one segment per lane (kernel 2; the library's rule from
+    4608 segments on) or one per wave (1): identical streams, and
     each decoder inverts the other's output; long segments cross several
     model rescales."""
-    from vcf_amd import _lib as L
     rng = np.random.Generator(np.random.PCG64(seg_len + prior))
     n = 200_003
     base = np.where(rng.random(n) < 0.97, 128, rng.integers(0, 256, n))
     sym = np.clip(base + (rng.random(n) < 0.3) * rng.integers(-2, 3, n), 0, 255).astype(np.uint8)
     sym[:5000] = rng.integers(0, 256, 5000)           # a noisy stretch: wide ranges, frequent rescales
     sym[-70:] = 255
-    try:
-        L.call("vcf_cbaac_tiled_set_variant", 1)
-        c1 = T.TiledCoder(0, seg_len, prior=prior)
-        s1, p1 = c1.encode(sym)
-        L.call("vcf_cbaac_tiled_set_variant", 2)
-        c0 = T.TiledCoder(0, seg_len, prior=prior)
-        s0, p0 = c0.encode(sym)
-        assert list(s0) == list(s1) and p0 == p1
-        pr = c0.last_prior if prior else None
-        assert np.array_equal(c0.decode(p0, s0, n, pr), sym)     # lane decoder
-        L.call("vcf_cbaac_tiled_set_variant", 1)
-        assert np.array_equal(c1.decode(p0, s0, n, pr), sym)     # wave decoder, same stream
-    finally:
-        L.call("vcf_cbaac_tiled_set_variant", 0)
+    c1 = T.TiledCoder(0, seg_len, prior=prior, kernel=1)
+    s1, p1 = c1.encode(sym)
+    c0 = T.TiledCoder(0, seg_len, prior=prior, kernel=2)
+    s0, p0 = c0.encode(sym)
+    assert list(s0) == list(s1) and p0 == p1
+    pr = c0.last_prior if prior else None
+    assert np.array_equal(c0.decode(p0, s0, n, pr), sym)     # lane decoder
+    assert np.array_equal(c1.decode(p0, s0, n, pr), sym)     # wave decoder, same stream
+
+
+def test_two_threads_each_hold_their_own_kernel():
+    """The kernel choice travels with the call: two host threads, each with its
+    own Stream and its own symbols, one always coding a wave per segment (1) and
+    the other a lane per segment (2), at the same time.  79 segments: more than
+    the lane kernel's 64 per workgroup and no multiple of it.  Every round's
+    sizes and payload equal the host coder's, fresh and prior-seeded, and every
+    decode gives the thread's array back."""
+    import threading
+    from vcf_amd.device import Stream
+    n, seg_len, rounds = 20_001, 256, 3
+    start, failed = threading.Barrier(2), []
+
+    def work(kernel, seed):
+        try:
+            rng = np.random.Generator(np.random.PCG64(seed))
+            sym = np.clip(np.rint(rng.laplace(128, 2.5, n)), 0, 255).astype(np.uint8)
+            st = Stream()
+            plain, seeded = (T.TiledCoder(0, seg_len, stream=st, prior=p, kernel=kernel) for p in (False, True))
+            host = T.host_segments(sym, 0, seg_len)
+            host_p = T.host_segments_prior(sym, T.prior_of(sym), seg_len)
+            start.wait(60)
+            for r in range(rounds):
+                for c, want in ((plain, host), (seeded, host_p)):
+                    sizes, payload = c.encode(sym)
+                    assert list(sizes) == [len(h) for h in want] and payload == b"".join(want), (kernel, r, c.prior)
+                    assert np.array_equal(c.decode(payload, sizes, n, c.last_prior), sym), (kernel, r, c.prior)
+        except BaseException as e:                     # the main thread reports it
+            start.abort()
+            failed.append((kernel, e))
+
+    threads = [threading.Thread(target=work, args=(k, 100 + k)) for k in (1, 2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not failed, failed
+
+
+def test_default_kernel_never_loads_the_ab_library():
+    """kernel 0 is the product's own entry: a process that never asks for another
+    choice round-trips without libvcf_amd_ab.so (a fresh process: this one's other
+    tests load it)."""
+    import subprocess
+    import sys
+    code = ("import numpy as np\n"
+            "from vcf_amd import _lib as L, tcbaac as T\n"
+            "sym = (np.arange(20_001) % 7).astype(np.uint8)\n"
+            "for prior in (False, True):\n"
+            "    c = T.TiledCoder(0, 256, prior=prior)\n"
+            "    sizes, payload = c.encode(sym)\n"
+            "    assert np.array_equal(c.decode(payload, sizes, sym.size, c.last_prior), sym)\n"
+            "enc = T.encode_frames_device(T.DeviceBuffer.from_array(sym), 1, sym.size, 0, 256, prior=True)\n"
+            "assert len(enc) == 1 and L._ab is None\n")
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120,
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert p.returncode == 0, p.stderr[-1500:]
 
 
 def test_lane_kernels_on_dct_indices_many_segments():
@@ -330,12 +381,9 @@ def test_batch_decode_frames(variant):
                        DeviceBuffer.from_array(priors))
     stride = n + 3                                   # unaligned output frames
     out = DeviceBuffer(F * stride)
-    try:
-        L.call("vcf_cbaac_tiled_set_variant", variant)
-        L.call("vcf_cbaac_tiled_decode_frames", src.ptr, doffs.ptr, F, n, 0, dpr.ptr, seg, out.ptr, stride, None)
-        got = out.download(np.empty(F * stride, np.uint8))
-    finally:
-        L.call("vcf_cbaac_tiled_set_variant", 0)
+    L.call_ab("vcf_cbaac_tiled_decode_frames_variant", variant, src.ptr, doffs.ptr, F, n, 0, dpr.ptr, seg, out.ptr, stride,
+              None)
+    got = out.download(np.empty(F * stride, np.uint8))
     for f in range(F):
         assert np.array_equal(got[f * stride:f * stride + n], frames[f]), f
 
@@ -356,23 +404,18 @@ def test_class_prior_segments_equal_host_coder(variant, order, seg_len, nclass):
     vcf_cbaac_encode_prior of that segment with its class's row, with one
     wave (1) or one lane (2, order 0) per segment; both decoders invert it.
     nclass = 200 > some frames' segment count leaves rows with no segments."""
-    from vcf_amd import _lib as L
     rng = np.random.Generator(np.random.PCG64(seg_len + nclass))
     lap = np.clip(np.rint(rng.laplace(128, 1.5, 300_001)), 0, 255).astype(np.uint8)
     lap[100_000:140_000] = 128
     for name, sym in (("dct", _dct_indices()), ("laplace", lap)):
-        try:
-            L.call("vcf_cbaac_tiled_set_variant", variant)
-            c = T.TiledCoder(order, seg_len, prior=True, nclass=nclass)
-            sizes, payload = c.encode(sym)
-            prior = T.prior_of(sym, nclass, seg_len)
-            assert np.array_equal(c.last_prior, prior), name
-            host = T.host_segments_prior(sym, prior, seg_len, order)
-            assert list(sizes) == [len(h) for h in host], name
-            assert payload == b"".join(host), name
-            assert np.array_equal(c.decode(payload, sizes, sym.size, prior), sym), name
-        finally:
-            L.call("vcf_cbaac_tiled_set_variant", 0)
+        c = T.TiledCoder(order, seg_len, prior=True, nclass=nclass, kernel=variant)
+        sizes, payload = c.encode(sym)
+        prior = T.prior_of(sym, nclass, seg_len)
+        assert np.array_equal(c.last_prior, prior), name
+        host = T.host_segments_prior(sym, prior, seg_len, order)
+        assert list(sizes) == [len(h) for h in host], name
+        assert payload == b"".join(host), name
+        assert np.array_equal(c.decode(payload, sizes, sym.size, prior), sym), name
 
 
 def test_class_priors_cut_the_rate_of_short_segments():

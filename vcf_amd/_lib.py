@@ -138,7 +138,6 @@ SIGNATURES = {
     "vcf_dwt_dz_encode_lift": [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
     "vcf_dwt_dz_decode_lift": [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
     "vcf_ipp_block_match": [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
-    "vcf_ipp_set_full_search_variant": [_I32],
     "vcf_ipp_motion_compensate": [_P, _P, _I32, _I32, _I32, _P, _P],
     "vcf_ipp_residual": [_P, _P, _I64, _P, _P],
     "vcf_ipp_reconstruct": [_P, _P, _I64, _P, _P],
@@ -166,7 +165,6 @@ SIGNATURES = {
     "vcf_zlib_strips": [_P, _I64, _I64, _I32, _I32, _P, _I64, _P, _P, _P],
     "vcf_deadzone_quantize": [_P, _I32, _I64, _I32, _P, _P],
     "vcf_deadzone_dequantize": [_P, _I32, _I64, _I32, _P, _P],
-    "vcf_cbaac_tiled_set_variant": [_I32],
     "vcf_cbaac_tiled_segments": [_I64, _I64],
     "vcf_cbaac_tiled_frames_workspace": [_I64, _I64, _I64],
     "vcf_cbaac_tiled_prior_frames": [_P, _I64, _I64, _I64, _P, _P, _P],
@@ -243,6 +241,10 @@ AB_SIGNATURES = {
     "vcf_dwt_dz_decode_lift_sched": [_PSCHED] + _DWT_ARGS,
     "vcf_inflate_strips_wincheck": [_P, _P, _P, _I64, _P, _P, _P, _P, _P, _P],
 }
+# the product entries with two kernels: their *_variant twins take the choice in front
+KERNEL_CHOICE = ("vcf_ipp_block_match",) + tuple(
+    f"vcf_cbaac_tiled_{d}{s}" for s in ("", "_prior", "_frames", "_classes") for d in ("encode", "decode"))
+AB_SIGNATURES.update({name + "_variant": [_I32] + SIGNATURES[name] for name in KERNEL_CHOICE})
 
 _lib = None
 _ab = None
@@ -332,6 +334,12 @@ def call_ab(name: str, *args) -> int:
 
 
 # A/B scripts: variant 0 = the product entry point, others = the A/B library's
+def call_v(kernel: int, name: str, *args) -> int:
+    """An entry of KERNEL_CHOICE: kernel 0 = the product's own name and rule,
+    another choice = its twin in the A/B library."""
+    return call(name, *args) if kernel == 0 else call_ab(name + "_variant", kernel, *args)
+
+
 def dct_encode_v(variant, *args):
     return call("vcf_dct_dz_encode", *args) if variant == 0 else call_ab("vcf_dct_dz_encode_variant", variant, *args)
 

@@ -981,11 +981,8 @@ __global__ __launch_bounds__(kLW) void cbaac_lane_decode_kernel(const uint8_t *_
 
 int64_t slot_words_for(int64_t seg_len) { return (vcf_cbaac_bound(seg_len) + 3) / 4; }
 
-// 0 = automatic (order 0: one lane per segment from kLaneMinEncode /
-// kLaneMinDecode segments on), 1 = one wave per segment, 2 = one lane per
-// segment (order 0; A/B)
-int g_tiled_variant = 0;
-// Crossovers measured on MI355X at 32768-symbol segments (scripts/
+// Order 0 codes one lane per segment from this many segments on (all frames of
+// a call).  Crossovers measured on MI355X at 32768-symbol segments (scripts/
 // bench_tcbaac_lane.py, profiles/r03_tcbaac_lane.jsonl): a wave per segment
 // fills the 1024 SIMDs from ~1000 segments on and then grows linearly (encode
 // 16.3 ms at 3038 segments, 39.0 at 12150; decode 21.9 / 63.0), a lane per
@@ -1380,19 +1377,165 @@ int check_2d(int64_t n_frames, int64_t H, int64_t W, int64_t C, int64_t th, int6
     return VCF_OK;
 }
 
+// one lane per segment when there are enough segments to fill waves with them
+// (a lane codes a symbol in about twice a wave's time, but 64 segments at once).
+// kernel: 0 = this rule, 1 = a wave per segment, 2 = a lane per segment (order 0)
+bool use_lanes(int32_t kernel, int32_t order, int64_t total_segments, bool decode)
+{
+    if (order != 0 || kernel == 1) return false;
+    return kernel == 2 || total_segments >= (decode ? kLaneMinDecode : kLaneMinEncode);
+}
+
+int tiled_encode(int32_t kernel, const uint8_t *sym_dev, int64_t n_frames, int64_t n, int64_t sym_stride,
+                 int32_t order, int64_t seg_len, uint8_t *out_dev, int64_t out_capacity, int64_t *seg_bytes_dev,
+                 int32_t *trace_dev, void *ws_dev, void *stream, const uint16_t *prior_dev = nullptr,
+                 int64_t prior_stride = 0, int32_t nclass = 1)
+{
+    if (int s = check_args(n, order, seg_len)) return s;
+    if (int s = check_frames(n_frames)) return s;
+    const int64_t ns = vcf_cbaac_tiled_segments(n, seg_len);
+    if (!seg_bytes_dev) return set_error(VCF_ERR_INVALID, "null seg_bytes");
+    hipStream_t st = (hipStream_t)stream;
+    if (ns == 0) return hip_check(hipMemsetAsync(seg_bytes_dev, 0, 8 * n_frames, st), "hipMemsetAsync");
+    if (!sym_dev || !ws_dev || (!trace_dev && !out_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
+    if (ns > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many segments");
+    const int64_t sw = slot_words_for(seg_len);
+    const EncodeWs ws(ws_dev, n_frames, ns, sw);
+    Frames fr;
+    fr.sym_stride = sym_stride;
+    fr.prior_stride = prior_stride;
+    fr.nclass = nclass;
+    const dim3 grid((unsigned)ns, (unsigned)n_frames);
+    if (!trace_dev && use_lanes(kernel, order, ns * n_frames, false)) {   // one lane per segment
+        const dim3 lg((unsigned)((ns + kLW - 1) / kLW), (unsigned)n_frames);
+        if (prior_dev) cbaac_lane_encode_kernel<true><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, ws.slots, sw, ws.bits, prior_dev, fr);
+        else cbaac_lane_encode_kernel<false><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, ws.slots, sw, ws.bits, nullptr, fr);
+    } else if (trace_dev) {
+        if (n_frames != 1) return set_error(VCF_ERR_INVALID, "traces take one frame");
+        if (order == 0) cbaac_tiled_encode_kernel<0, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, trace_dev, prior_dev, fr);
+        else cbaac_tiled_encode_kernel<1, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, trace_dev, prior_dev, fr);
+    } else {
+        if (order == 0) cbaac_tiled_encode_kernel<0, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, nullptr, prior_dev, fr);
+        else cbaac_tiled_encode_kernel<1, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, nullptr, prior_dev, fr);
+    }
+    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_encode_kernel")) return s;
+    return scan_and_pack(ws, n_frames, ns, sw, out_dev, out_capacity, seg_bytes_dev, st);
+}
+
+int tiled_decode(int32_t kernel, const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n_frames, int64_t n,
+                 int32_t order, int64_t seg_len, uint8_t *sym_dev, int64_t out_stride, void *stream,
+                 const uint16_t *prior_dev, int64_t prior_stride, int32_t nclass = 1)
+{
+    if (int s = check_args(n, order, seg_len)) return s;
+    if (int s = check_frames(n_frames)) return s;
+    const int64_t ns = vcf_cbaac_tiled_segments(n, seg_len);
+    if (ns == 0) return VCF_OK;
+    if (!in_dev || !seg_offsets_dev || !sym_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    if (ns > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many segments");
+    hipStream_t st = (hipStream_t)stream;
+    Frames fr;
+    fr.out_stride = out_stride;
+    fr.prior_stride = prior_stride;
+    fr.nclass = nclass;
+    const dim3 grid((unsigned)ns, (unsigned)n_frames);
+    if (use_lanes(kernel, order, ns * n_frames, true)) {   // one lane per segment
+        const dim3 lg((unsigned)((ns + kLW - 1) / kLW), (unsigned)n_frames);
+        if (prior_dev)
+            cbaac_lane_decode_kernel<true><<<lg, kLW, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, ns, sym_dev, prior_dev, fr);
+        else
+            cbaac_lane_decode_kernel<false><<<lg, kLW, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, ns, sym_dev, nullptr, fr);
+        return hip_check(hipGetLastError(), "cbaac_lane_decode_kernel");
+    }
+    if (order == 0) cbaac_tiled_decode_kernel<0><<<grid, 64, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, sym_dev, prior_dev, fr);
+    else cbaac_tiled_decode_kernel<1><<<grid, 64, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, sym_dev, prior_dev, fr);
+    return hip_check(hipGetLastError(), "cbaac_tiled_decode_kernel");
+}
+
 }  // namespace
+
+// ---- the entries with two kernels (vcf_internal.h): vcf_cbaac_tiled_<name> passes kernel 0,
+// the A/B library's vcf_cbaac_tiled_<name>_variant the caller's choice ---------------------
+int cbaac_tiled_encode(int32_t kernel, const uint8_t *sym_dev, int64_t n, int32_t order, int64_t seg_len,
+                       uint8_t *out_dev, int64_t out_capacity, int64_t *seg_bytes_dev, void *ws_dev, void *stream)
+{
+    if (out_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
+    if (n > 0 && !out_dev) return set_error(VCF_ERR_INVALID, "null output buffer");
+    return tiled_encode(kernel, sym_dev, 1, n, 0, order, seg_len, out_dev, out_capacity, seg_bytes_dev, nullptr, ws_dev,
+                        stream);
+}
+
+int cbaac_tiled_decode(int32_t kernel, const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n, int32_t order,
+                       int64_t seg_len, uint8_t *sym_dev, void *stream)
+{
+    return tiled_decode(kernel, in_dev, seg_offsets_dev, 1, n, order, seg_len, sym_dev, 0, stream, nullptr, 0);
+}
+
+int cbaac_tiled_encode_prior(int32_t kernel, const uint8_t *sym_dev, int64_t n, int32_t order,
+                             const uint16_t *prior_dev, int64_t seg_len, uint8_t *out_dev, int64_t out_capacity,
+                             int64_t *seg_bytes_dev, void *ws_dev, void *stream)
+{
+    if (out_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
+    if (n > 0 && (!out_dev || !prior_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
+    if (int s = check_prior_aligned(prior_dev, "prior_dev")) return s;
+    return tiled_encode(kernel, sym_dev, 1, n, 0, order, seg_len, out_dev, out_capacity, seg_bytes_dev, nullptr, ws_dev,
+                        stream, prior_dev);
+}
+
+int cbaac_tiled_decode_prior(int32_t kernel, const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n,
+                             int32_t order, const uint16_t *prior_dev, int64_t seg_len, uint8_t *sym_dev, void *stream)
+{
+    if (n > 0 && !prior_dev) return set_error(VCF_ERR_INVALID, "null prior");
+    if (int s = check_prior_aligned(prior_dev, "prior_dev")) return s;
+    return tiled_decode(kernel, in_dev, seg_offsets_dev, 1, n, order, seg_len, sym_dev, 0, stream, prior_dev, 0);
+}
+
+int cbaac_tiled_encode_frames(int32_t kernel, const uint8_t *sym_dev, int64_t n_frames, int64_t frame_symbols,
+                              int64_t frame_stride, int32_t order, const uint16_t *priors_dev, int64_t seg_len,
+                              uint8_t *out_dev, int64_t out_frame_capacity, int64_t *seg_bytes_dev, void *ws_dev,
+                              void *stream)
+{
+    if (out_frame_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
+    if (frame_symbols > 0 && !out_dev) return set_error(VCF_ERR_INVALID, "null output buffer");
+    if (int s = check_prior_aligned(priors_dev, "priors_dev")) return s;
+    return tiled_encode(kernel, sym_dev, n_frames, frame_symbols, frame_stride, order, seg_len, out_dev,
+                        out_frame_capacity, seg_bytes_dev, nullptr, ws_dev, stream, priors_dev, priors_dev ? 256 : 0);
+}
+
+int cbaac_tiled_decode_frames(int32_t kernel, const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n_frames,
+                              int64_t frame_symbols, int32_t order, const uint16_t *priors_dev, int64_t seg_len,
+                              uint8_t *sym_dev, int64_t out_frame_stride, void *stream)
+{
+    if (int s = check_prior_aligned(priors_dev, "priors_dev")) return s;
+    return tiled_decode(kernel, in_dev, seg_offsets_dev, n_frames, frame_symbols, order, seg_len, sym_dev,
+                        out_frame_stride, stream, priors_dev, priors_dev ? 256 : 0);
+}
+
+int cbaac_tiled_encode_classes(int32_t kernel, const uint8_t *sym_dev, int64_t n_frames, int64_t frame_symbols,
+                               int64_t frame_stride, int32_t order, const uint16_t *priors_dev, int32_t nclass,
+                               int64_t seg_len, uint8_t *out_dev, int64_t out_frame_capacity, int64_t *seg_bytes_dev,
+                               void *ws_dev, void *stream)
+{
+    if (int s = check_classes(nclass, priors_dev)) return s;
+    if (out_frame_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
+    if (frame_symbols > 0 && (!out_dev || !priors_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
+    return tiled_encode(kernel, sym_dev, n_frames, frame_symbols, frame_stride, order, seg_len, out_dev,
+                        out_frame_capacity, seg_bytes_dev, nullptr, ws_dev, stream, priors_dev, 256LL * nclass, nclass);
+}
+
+int cbaac_tiled_decode_classes(int32_t kernel, const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n_frames,
+                               int64_t frame_symbols, int32_t order, const uint16_t *priors_dev, int32_t nclass,
+                               int64_t seg_len, uint8_t *sym_dev, int64_t out_frame_stride, void *stream)
+{
+    if (int s = check_classes(nclass, priors_dev)) return s;
+    if (frame_symbols > 0 && !priors_dev) return set_error(VCF_ERR_INVALID, "null prior");
+    return tiled_decode(kernel, in_dev, seg_offsets_dev, n_frames, frame_symbols, order, seg_len, sym_dev,
+                        out_frame_stride, stream, priors_dev, 256LL * nclass, nclass);
+}
 }  // namespace vcf
 
 using namespace vcf;
 
 extern "C" {
-
-int vcf_cbaac_tiled_set_variant(int32_t variant)
-{
-    if (variant < 0 || variant > 2) return set_error(VCF_ERR_INVALID, "tiled CBAAC variant %d (0, 1, 2)", variant);
-    g_tiled_variant = variant;
-    return VCF_OK;
-}
 
 int64_t vcf_cbaac_tiled_segments(int64_t n, int64_t seg_len)
 {
@@ -1417,99 +1560,23 @@ int64_t vcf_cbaac_tiled_frames_workspace(int64_t n_frames, int64_t frame_symbols
     return n_frames <= 0 ? 0 : n_frames * vcf_cbaac_tiled_workspace(frame_symbols, seg_len);
 }
 
-// one lane per segment when there are enough segments to fill waves with them
-// (a lane codes a symbol in about twice a wave's time, but 64 segments at once)
-static bool use_lanes(int32_t order, int64_t total_segments, bool decode)
-{
-    if (order != 0 || g_tiled_variant == 1) return false;
-    return g_tiled_variant == 2 || total_segments >= (decode ? kLaneMinDecode : kLaneMinEncode);
-}
-
-static int tiled_encode(const uint8_t *sym_dev, int64_t n_frames, int64_t n, int64_t sym_stride, int32_t order,
-                        int64_t seg_len, uint8_t *out_dev, int64_t out_capacity, int64_t *seg_bytes_dev,
-                        int32_t *trace_dev, void *ws_dev, void *stream, const uint16_t *prior_dev = nullptr,
-                        int64_t prior_stride = 0, int32_t nclass = 1)
-{
-    if (int s = check_args(n, order, seg_len)) return s;
-    if (int s = check_frames(n_frames)) return s;
-    const int64_t ns = vcf_cbaac_tiled_segments(n, seg_len);
-    if (!seg_bytes_dev) return set_error(VCF_ERR_INVALID, "null seg_bytes");
-    hipStream_t st = (hipStream_t)stream;
-    if (ns == 0) return hip_check(hipMemsetAsync(seg_bytes_dev, 0, 8 * n_frames, st), "hipMemsetAsync");
-    if (!sym_dev || !ws_dev || (!trace_dev && !out_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
-    if (ns > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many segments");
-    const int64_t sw = slot_words_for(seg_len);
-    const EncodeWs ws(ws_dev, n_frames, ns, sw);
-    Frames fr;
-    fr.sym_stride = sym_stride;
-    fr.prior_stride = prior_stride;
-    fr.nclass = nclass;
-    const dim3 grid((unsigned)ns, (unsigned)n_frames);
-    if (!trace_dev && use_lanes(order, ns * n_frames, false)) {   // one lane per segment
-        const dim3 lg((unsigned)((ns + kLW - 1) / kLW), (unsigned)n_frames);
-        if (prior_dev) cbaac_lane_encode_kernel<true><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, ws.slots, sw, ws.bits, prior_dev, fr);
-        else cbaac_lane_encode_kernel<false><<<lg, kLW, 0, st>>>(sym_dev, n, seg_len, ns, ws.slots, sw, ws.bits, nullptr, fr);
-    } else if (trace_dev) {
-        if (n_frames != 1) return set_error(VCF_ERR_INVALID, "traces take one frame");
-        if (order == 0) cbaac_tiled_encode_kernel<0, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, trace_dev, prior_dev, fr);
-        else cbaac_tiled_encode_kernel<1, true><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, trace_dev, prior_dev, fr);
-    } else {
-        if (order == 0) cbaac_tiled_encode_kernel<0, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, nullptr, prior_dev, fr);
-        else cbaac_tiled_encode_kernel<1, false><<<grid, 64, 0, st>>>(sym_dev, n, seg_len, ws.slots, sw, ws.bits, nullptr, prior_dev, fr);
-    }
-    if (int s = hip_check(hipGetLastError(), "cbaac_tiled_encode_kernel")) return s;
-    return scan_and_pack(ws, n_frames, ns, sw, out_dev, out_capacity, seg_bytes_dev, st);
-}
-
 int vcf_cbaac_tiled_encode(const uint8_t *sym_dev, int64_t n, int32_t order, int64_t seg_len, uint8_t *out_dev,
                            int64_t out_capacity, int64_t *seg_bytes_dev, void *ws_dev, void *stream)
 {
-    if (out_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
-    if (n > 0 && !out_dev) return set_error(VCF_ERR_INVALID, "null output buffer");
-    return tiled_encode(sym_dev, 1, n, 0, order, seg_len, out_dev, out_capacity, seg_bytes_dev, nullptr, ws_dev,
-                        stream);
+    return cbaac_tiled_encode(0, sym_dev, n, order, seg_len, out_dev, out_capacity, seg_bytes_dev, ws_dev, stream);
 }
 
 int vcf_cbaac_tiled_trace(const uint8_t *sym_dev, int64_t n, int32_t order, int64_t seg_len, int32_t *triples_dev,
                           int64_t *seg_bytes_dev, void *ws_dev, void *stream)
 {
     if (n > 0 && !triples_dev) return set_error(VCF_ERR_INVALID, "null trace buffer");
-    return tiled_encode(sym_dev, 1, n, 0, order, seg_len, nullptr, 0, seg_bytes_dev, triples_dev, ws_dev, stream);
-}
-
-static int tiled_decode(const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n_frames, int64_t n,
-                        int32_t order, int64_t seg_len, uint8_t *sym_dev, int64_t out_stride, void *stream,
-                        const uint16_t *prior_dev, int64_t prior_stride, int32_t nclass = 1)
-{
-    if (int s = check_args(n, order, seg_len)) return s;
-    if (int s = check_frames(n_frames)) return s;
-    const int64_t ns = vcf_cbaac_tiled_segments(n, seg_len);
-    if (ns == 0) return VCF_OK;
-    if (!in_dev || !seg_offsets_dev || !sym_dev) return set_error(VCF_ERR_INVALID, "null buffer");
-    if (ns > 0x7FFFFFFF) return set_error(VCF_ERR_INVALID, "too many segments");
-    hipStream_t st = (hipStream_t)stream;
-    Frames fr;
-    fr.out_stride = out_stride;
-    fr.prior_stride = prior_stride;
-    fr.nclass = nclass;
-    const dim3 grid((unsigned)ns, (unsigned)n_frames);
-    if (use_lanes(order, ns * n_frames, true)) {   // one lane per segment
-        const dim3 lg((unsigned)((ns + kLW - 1) / kLW), (unsigned)n_frames);
-        if (prior_dev)
-            cbaac_lane_decode_kernel<true><<<lg, kLW, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, ns, sym_dev, prior_dev, fr);
-        else
-            cbaac_lane_decode_kernel<false><<<lg, kLW, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, ns, sym_dev, nullptr, fr);
-        return hip_check(hipGetLastError(), "cbaac_lane_decode_kernel");
-    }
-    if (order == 0) cbaac_tiled_decode_kernel<0><<<grid, 64, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, sym_dev, prior_dev, fr);
-    else cbaac_tiled_decode_kernel<1><<<grid, 64, 0, st>>>(in_dev, seg_offsets_dev, n, seg_len, sym_dev, prior_dev, fr);
-    return hip_check(hipGetLastError(), "cbaac_tiled_decode_kernel");
+    return tiled_encode(0, sym_dev, 1, n, 0, order, seg_len, nullptr, 0, seg_bytes_dev, triples_dev, ws_dev, stream);
 }
 
 int vcf_cbaac_tiled_decode(const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n, int32_t order,
                            int64_t seg_len, uint8_t *sym_dev, void *stream)
 {
-    return tiled_decode(in_dev, seg_offsets_dev, 1, n, order, seg_len, sym_dev, 0, stream, nullptr, 0);
+    return cbaac_tiled_decode(0, in_dev, seg_offsets_dev, n, order, seg_len, sym_dev, stream);
 }
 
 static int tiled_prior(const uint8_t *sym_dev, int64_t n_frames, int64_t n, int64_t sym_stride, uint16_t *prior_dev,
@@ -1539,19 +1606,14 @@ int vcf_cbaac_tiled_encode_prior(const uint8_t *sym_dev, int64_t n, int32_t orde
                                  int64_t seg_len, uint8_t *out_dev, int64_t out_capacity, int64_t *seg_bytes_dev,
                                  void *ws_dev, void *stream)
 {
-    if (out_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
-    if (n > 0 && (!out_dev || !prior_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
-    if (int s = check_prior_aligned(prior_dev, "prior_dev")) return s;
-    return tiled_encode(sym_dev, 1, n, 0, order, seg_len, out_dev, out_capacity, seg_bytes_dev, nullptr, ws_dev, stream,
-                        prior_dev);
+    return cbaac_tiled_encode_prior(0, sym_dev, n, order, prior_dev, seg_len, out_dev, out_capacity, seg_bytes_dev, ws_dev,
+                                    stream);
 }
 
 int vcf_cbaac_tiled_decode_prior(const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n, int32_t order,
                                  const uint16_t *prior_dev, int64_t seg_len, uint8_t *sym_dev, void *stream)
 {
-    if (n > 0 && !prior_dev) return set_error(VCF_ERR_INVALID, "null prior");
-    if (int s = check_prior_aligned(prior_dev, "prior_dev")) return s;
-    return tiled_decode(in_dev, seg_offsets_dev, 1, n, order, seg_len, sym_dev, 0, stream, prior_dev, 0);
+    return cbaac_tiled_decode_prior(0, in_dev, seg_offsets_dev, n, order, prior_dev, seg_len, sym_dev, stream);
 }
 
 // ---- batches of frames: one launch per stage for all of them -------------------------
@@ -1566,20 +1628,16 @@ int vcf_cbaac_tiled_encode_frames(const uint8_t *sym_dev, int64_t n_frames, int6
                                   uint8_t *out_dev, int64_t out_frame_capacity, int64_t *seg_bytes_dev, void *ws_dev,
                                   void *stream)
 {
-    if (out_frame_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
-    if (frame_symbols > 0 && !out_dev) return set_error(VCF_ERR_INVALID, "null output buffer");
-    if (int s = check_prior_aligned(priors_dev, "priors_dev")) return s;
-    return tiled_encode(sym_dev, n_frames, frame_symbols, frame_stride, order, seg_len, out_dev, out_frame_capacity,
-                        seg_bytes_dev, nullptr, ws_dev, stream, priors_dev, priors_dev ? 256 : 0);
+    return cbaac_tiled_encode_frames(0, sym_dev, n_frames, frame_symbols, frame_stride, order, priors_dev, seg_len, out_dev,
+                                     out_frame_capacity, seg_bytes_dev, ws_dev, stream);
 }
 
 int vcf_cbaac_tiled_decode_frames(const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n_frames,
                                   int64_t frame_symbols, int32_t order, const uint16_t *priors_dev, int64_t seg_len,
                                   uint8_t *sym_dev, int64_t out_frame_stride, void *stream)
 {
-    if (int s = check_prior_aligned(priors_dev, "priors_dev")) return s;
-    return tiled_decode(in_dev, seg_offsets_dev, n_frames, frame_symbols, order, seg_len, sym_dev, out_frame_stride,
-                        stream, priors_dev, priors_dev ? 256 : 0);
+    return cbaac_tiled_decode_frames(0, in_dev, seg_offsets_dev, n_frames, frame_symbols, order, priors_dev, seg_len, sym_dev,
+                                     out_frame_stride, stream);
 }
 
 // ---- version 3: prior classes (consecutive runs of segments share a prior row) ----
@@ -1609,21 +1667,16 @@ int vcf_cbaac_tiled_encode_classes(const uint8_t *sym_dev, int64_t n_frames, int
                                    int64_t seg_len, uint8_t *out_dev, int64_t out_frame_capacity,
                                    int64_t *seg_bytes_dev, void *ws_dev, void *stream)
 {
-    if (int s = check_classes(nclass, priors_dev)) return s;
-    if (out_frame_capacity < 0) return set_error(VCF_ERR_INVALID, "negative capacity");
-    if (frame_symbols > 0 && (!out_dev || !priors_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
-    return tiled_encode(sym_dev, n_frames, frame_symbols, frame_stride, order, seg_len, out_dev, out_frame_capacity,
-                        seg_bytes_dev, nullptr, ws_dev, stream, priors_dev, 256LL * nclass, nclass);
+    return cbaac_tiled_encode_classes(0, sym_dev, n_frames, frame_symbols, frame_stride, order, priors_dev, nclass, seg_len,
+                                      out_dev, out_frame_capacity, seg_bytes_dev, ws_dev, stream);
 }
 
 int vcf_cbaac_tiled_decode_classes(const uint8_t *in_dev, const int64_t *seg_offsets_dev, int64_t n_frames,
                                    int64_t frame_symbols, int32_t order, const uint16_t *priors_dev, int32_t nclass,
                                    int64_t seg_len, uint8_t *sym_dev, int64_t out_frame_stride, void *stream)
 {
-    if (int s = check_classes(nclass, priors_dev)) return s;
-    if (frame_symbols > 0 && !priors_dev) return set_error(VCF_ERR_INVALID, "null prior");
-    return tiled_decode(in_dev, seg_offsets_dev, n_frames, frame_symbols, order, seg_len, sym_dev, out_frame_stride,
-                        stream, priors_dev, 256LL * nclass, nclass);
+    return cbaac_tiled_decode_classes(0, in_dev, seg_offsets_dev, n_frames, frame_symbols, order, priors_dev, nclass, seg_len,
+                                      sym_dev, out_frame_stride, stream);
 }
 
 // ---- version 4: tiles with a two-dimensional context ----------------------------------

@@ -428,18 +428,12 @@ __global__ __launch_bounds__(256) void ipp_recon_kernel(const uint8_t *__restric
 
 unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
-int g_full_search_variant = 0;   // 0: word kernel when bs % 4 == 0; 1: byte kernel (A/B)
-int ipp_full_search_variant() { return g_full_search_variant; }
-
 }  // namespace
-}  // namespace vcf
 
-using namespace vcf;
-
-extern "C" {
-
-int vcf_ipp_block_match(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, int32_t bs,
-                        int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream)
+// variant 0: the word kernels when bs % 4 == 0 (full search) or bs == 16 (three-step); 1: the byte
+// kernels (vcf_ipp_block_match_variant of the A/B library)
+int ipp_block_match(int32_t variant, const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W,
+                    int32_t bs, int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream)
 {
     if (!ref_rgb_dev || !cur_rgb_dev || !mv_dev || !gray_workspace_dev) return set_error(VCF_ERR_INVALID, "null buffer");
     if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad frame shape");
@@ -453,11 +447,11 @@ int vcf_ipp_block_match(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, 
     hipLaunchKernelGGL(ipp_gray_kernel, dim3(blocks_for(npx)), dim3(256), 0, s, ref_rgb_dev, rg, npx);
     hipLaunchKernelGGL(ipp_gray_kernel, dim3(blocks_for(npx)), dim3(256), 0, s, cur_rgb_dev, cg, npx);
     if (fast) {
-        if (bs == 16 && ipp_full_search_variant() == 0)
+        if (bs == 16 && variant == 0)
             hipLaunchKernelGGL(ipp_tss16_kernel, dim3(nbx, nby), dim3(64), 0, s, rg, cg, H, W, sr, mv_dev);
         else
             hipLaunchKernelGGL(ipp_tss_kernel, dim3(nbx, nby), dim3(64), 0, s, rg, cg, H, W, bs, sr, mv_dev);
-    } else if (bs % 4 != 0 || ipp_full_search_variant() == 1) {
+    } else if (bs % 4 != 0 || variant == 1) {
         hipLaunchKernelGGL(ipp_full_search_kernel, dim3(nbx, nby), dim3(256), 0, s, rg, cg, H, W, bs, sr, mv_dev);
     } else {
         const int ncand = (2 * sr + 1) * (2 * sr + 1);
@@ -473,12 +467,16 @@ int vcf_ipp_block_match(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, 
     }
     return hip_check(hipGetLastError(), "ipp block match launch");
 }
+}  // namespace vcf
 
-int vcf_ipp_set_full_search_variant(int32_t variant)
+using namespace vcf;
+
+extern "C" {
+
+int vcf_ipp_block_match(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, int32_t bs,
+                        int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream)
 {
-    if (variant < 0 || variant > 1) return set_error(VCF_ERR_INVALID, "unknown full-search variant %d", variant);
-    g_full_search_variant = variant;
-    return VCF_OK;
+    return ipp_block_match(0, ref_rgb_dev, cur_rgb_dev, H, W, bs, sr, fast, mv_dev, gray_workspace_dev, stream);
 }
 
 int vcf_ipp_motion_compensate(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,

@@ -17,8 +17,11 @@ def _rgb(a):
     return a
 
 
-def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, fast: bool = False) -> np.ndarray:
-    """IPP.block_matching (IPP_DCT.py:344-376) -> (H//bs, W//bs, 2) float32 (dx, dy)."""
+def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, fast: bool = False,
+                   variant: int = 0) -> np.ndarray:
+    """IPP.block_matching (IPP_DCT.py:344-376) -> (H//bs, W//bs, 2) float32 (dx, dy).
+    variant 0: word kernels (full search for bs % 4 == 0, parallel-round TSS for bs 16; the product's rule),
+    1: byte / serial kernels (the A/B library's twin; same vectors)."""
     ref, cur = _rgb(ref), _rgb(cur)
     H, W = ref.shape[:2]
     mv = np.zeros((H // bs, W // bs, 2), np.float32)
@@ -27,17 +30,12 @@ def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, 
     dr, dc = DeviceBuffer.from_array(ref), DeviceBuffer.from_array(cur)
     dm, dg = DeviceBuffer(mv.nbytes), DeviceBuffer(2 * H * W)
     try:
-        L.call("vcf_ipp_block_match", dr.ptr, dc.ptr, H, W, int(bs), int(sr), int(bool(fast)), dm.ptr, dg.ptr, None)
+        L.call_v(int(variant), "vcf_ipp_block_match", dr.ptr, dc.ptr, H, W, int(bs), int(sr), int(bool(fast)), dm.ptr,
+                 dg.ptr, None)
         return dm.download(mv)
     finally:
         for b in (dr, dc, dm, dg):
             b.free()
-
-
-def set_full_search_variant(variant: int) -> None:
-    """0: word kernels (full search for bs % 4 == 0, parallel-round TSS for bs 16; default),
-    1: byte / serial kernels (A/B; same vectors)."""
-    L.call("vcf_ipp_set_full_search_variant", int(variant))
 
 
 def motion_compensate(frame: np.ndarray, mv: np.ndarray, bs: int = 16) -> np.ndarray:

@@ -100,12 +100,14 @@ class TiledCoder:
     One coder owns one set of scratch buffers and one stream, so its calls
     are serialised by `lock` (the DCT CoDec's encode_fns/decode_fns call the
     entropy codec from a thread pool): a call's upload, kernels and download
-    never interleave with another thread's on the same buffers."""
+    never interleave with another thread's on the same buffers.
+    `kernel`: 0 = the library's rule, 1 = a wave per segment, 2 = a lane per
+    segment (order 0) -- the A/B library's twins, for tests and A/B scripts."""
 
     def __init__(self, order: int = 0, seg_len: int = DEFAULT_SEG, stream: Stream | None = None,
-                 prior: bool = False, nclass: int = 1):
+                 prior: bool = False, nclass: int = 1, kernel: int = 0):
         self.order, self.seg_len, self.prior = int(order), int(seg_len), bool(prior)
-        self.nclass = int(nclass)
+        self.nclass, self.kernel = int(nclass), int(kernel)
         if self.prior and self.order > 1:
             raise NotImplementedError("prior-seeded tiled CBAAC: orders 0 and 1")
         if self.nclass < 1 or (self.nclass > 1 and not self.prior):
@@ -134,20 +136,20 @@ class TiledCoder:
             pr, hist = self.scratch.get("prior", 512 * K), self.scratch.get("hist", 1024 * K)
             L.call("vcf_cbaac_tiled_prior_classes", sym.address(offset), 1, int(n), int(n), self.seg_len, K, pr.ptr,
                    hist.ptr, self.stream.handle)
-            L.call("vcf_cbaac_tiled_encode_classes", sym.address(offset), 1, int(n), int(n), self.order, pr.ptr, K,
-                   self.seg_len, out.ptr, cap, sb.ptr, ws.ptr, self.stream.handle)
+            L.call_v(self.kernel, "vcf_cbaac_tiled_encode_classes", sym.address(offset), 1, int(n), int(n), self.order,
+                     pr.ptr, K, self.seg_len, out.ptr, cap, sb.ptr, ws.ptr, self.stream.handle)
             self.last_prior = np.empty((K, 256), np.uint16)
             pr.download(self.last_prior, self.stream)
         elif self.prior:
             pr, hist = self.scratch.get("prior", 512), self.scratch.get("hist", 1024)
             L.call("vcf_cbaac_tiled_prior", sym.address(offset), int(n), pr.ptr, hist.ptr, self.stream.handle)
-            L.call("vcf_cbaac_tiled_encode_prior", sym.address(offset), int(n), self.order, pr.ptr, self.seg_len,
-                   out.ptr, cap, sb.ptr, ws.ptr, self.stream.handle)
+            L.call_v(self.kernel, "vcf_cbaac_tiled_encode_prior", sym.address(offset), int(n), self.order, pr.ptr,
+                     self.seg_len, out.ptr, cap, sb.ptr, ws.ptr, self.stream.handle)
             self.last_prior = np.empty(256, np.uint16)
             pr.download(self.last_prior, self.stream)
         else:
-            L.call("vcf_cbaac_tiled_encode", sym.address(offset), int(n), self.order, self.seg_len, out.ptr, cap,
-                   sb.ptr, ws.ptr, self.stream.handle)
+            L.call_v(self.kernel, "vcf_cbaac_tiled_encode", sym.address(offset), int(n), self.order, self.seg_len,
+                     out.ptr, cap, sb.ptr, ws.ptr, self.stream.handle)
         sizes = np.empty(ns + 1, np.int64)
         sb.download(sizes, self.stream)
         self.stream.synchronize()
@@ -212,17 +214,17 @@ class TiledCoder:
             prior = check_prior(prior)
             pr = self.scratch.get("prior_in", prior.nbytes)
             pr.upload(prior, self.stream)
-            L.call("vcf_cbaac_tiled_decode_classes", src.ptr, ob.ptr, 1, int(n), self.order, pr.ptr, prior.shape[0],
-                   self.seg_len, out.ptr, int(n), self.stream.handle)
+            L.call_v(self.kernel, "vcf_cbaac_tiled_decode_classes", src.ptr, ob.ptr, 1, int(n), self.order, pr.ptr,
+                     prior.shape[0], self.seg_len, out.ptr, int(n), self.stream.handle)
         elif prior is not None:
             prior = check_prior(prior)
             pr = self.scratch.get("prior_in", 512)
             pr.upload(prior, self.stream)
-            L.call("vcf_cbaac_tiled_decode_prior", src.ptr, ob.ptr, int(n), self.order, pr.ptr, self.seg_len,
-                   out.ptr, self.stream.handle)
+            L.call_v(self.kernel, "vcf_cbaac_tiled_decode_prior", src.ptr, ob.ptr, int(n), self.order, pr.ptr,
+                     self.seg_len, out.ptr, self.stream.handle)
         else:
-            L.call("vcf_cbaac_tiled_decode", src.ptr, ob.ptr, int(n), self.order, self.seg_len, out.ptr,
-                   self.stream.handle)
+            L.call_v(self.kernel, "vcf_cbaac_tiled_decode", src.ptr, ob.ptr, int(n), self.order, self.seg_len,
+                     out.ptr, self.stream.handle)
 
     def decode(self, payload: bytes, seg_bytes, n: int, prior=None) -> np.ndarray:
         with self.lock:
@@ -260,11 +262,11 @@ class FrameBatch:
     the code-streams."""
 
     def __init__(self, n_frames: int, frame_symbols: int, order: int = 0, seg_len: int = PRIOR_SEG,
-                 prior: bool = True, streams: int | None = None, nclass: int = 1):
+                 prior: bool = True, streams: int | None = None, nclass: int = 1, kernel: int = 0):
         lib = L.lib()
         self.n_frames, self.n = int(n_frames), int(frame_symbols)
         self.order, self.seg_len, self.prior = int(order), int(seg_len), bool(prior)
-        self.nclass = int(nclass)
+        self.nclass, self.kernel = int(nclass), int(kernel)
         if self.prior and self.order > 1:
             raise NotImplementedError("prior-seeded tiled CBAAC: orders 0 and 1")
         if self.nclass < 1 or (self.nclass > 1 and not self.prior):
@@ -300,16 +302,16 @@ class FrameBatch:
         if self.nclass > 1:
             L.call("vcf_cbaac_tiled_prior_classes", base, self.n_frames, self.n, stride, self.seg_len, self.nclass,
                    self.prior_dev.ptr, self.hist.ptr, h)
-            L.call("vcf_cbaac_tiled_encode_classes", base, self.n_frames, self.n, stride, self.order,
-                   self.prior_dev.ptr, self.nclass, self.seg_len, self.out.ptr, self.cap, self.sizes_dev.ptr,
-                   self.ws.ptr, h)
+            L.call_v(self.kernel, "vcf_cbaac_tiled_encode_classes", base, self.n_frames, self.n, stride, self.order,
+                     self.prior_dev.ptr, self.nclass, self.seg_len, self.out.ptr, self.cap, self.sizes_dev.ptr,
+                     self.ws.ptr, h)
             return
         if self.prior:
             L.call("vcf_cbaac_tiled_prior_frames", base, self.n_frames, self.n, stride, self.prior_dev.ptr,
                    self.hist.ptr, h)
-        L.call("vcf_cbaac_tiled_encode_frames", base, self.n_frames, self.n, stride, self.order,
-               self.prior_dev.ptr if self.prior else None, self.seg_len, self.out.ptr, self.cap, self.sizes_dev.ptr,
-               self.ws.ptr, h)
+        L.call_v(self.kernel, "vcf_cbaac_tiled_encode_frames", base, self.n_frames, self.n, stride, self.order,
+                 self.prior_dev.ptr if self.prior else None, self.seg_len, self.out.ptr, self.cap, self.sizes_dev.ptr,
+                 self.ws.ptr, h)
 
     def join(self, stream: Stream) -> None:
         """`stream` waits for the coding (no host synchronisation)."""
@@ -378,7 +380,7 @@ class FrameBatch:
 
 def encode_frames_device(sym: DeviceBuffer, n_frames: int, frame_symbols: int, order: int = 0,
                          seg_len: int = DEFAULT_SEG, prior: bool = False, streams: int = 4,
-                         after: Stream | None = None, offset: int = 0, nclass: int = 1):
+                         after: Stream | None = None, offset: int = 0, nclass: int = 1, kernel: int = 0):
     """Several frames' symbols, back to back in HBM from `offset`, each coded
     as its own tiled stream (its own prior with prior=True), all of them in
     one launch per stage (FrameBatch; `streams` is accepted for the earlier
@@ -386,7 +388,7 @@ def encode_frames_device(sym: DeviceBuffer, n_frames: int, frame_symbols: int, o
     (e.g. the DCT encode's); the coder waits for its work so far (an event),
     so the caller need not synchronise it first.
     -> [(segment byte counts, payload, prior or None)]."""
-    fb = FrameBatch(n_frames, frame_symbols, order, seg_len, prior, nclass=nclass)
+    fb = FrameBatch(n_frames, frame_symbols, order, seg_len, prior, nclass=nclass, kernel=kernel)
     fb.launch(sym, offset, after)
     return fb.download()
 
