@@ -32,6 +32,18 @@
  *     array the reference hands to its entropy codec (2D-DCT.py:364).
  *   - Work is enqueued on `stream` (a hipStream_t, NULL = default stream)
  *     and is asynchronous; synchronise with vcf_stream_sync.
+ *   - Alignment and extents.  A byte-typed frame pointer (uint8_t *: images,
+ *     index frames, luma workspaces) needs no alignment: a pointer into the
+ *     middle of a larger allocation gives the same bytes, the kernels taking
+ *     their byte paths where the address does not allow a wider access.  A
+ *     typed pointer (int16_t, uint16_t, int32_t, float, double, int64_t)
+ *     needs the alignment of its element; a misaligned one is VCF_ERR_INVALID
+ *     before any device work, nothing written.  Every call writes only the
+ *     bytes of the output extent its entry states, n_frames x the frame size
+ *     from the pointer on unless said otherwise.  Stated per entry point for
+ *     every transform, IPP, VQ and pixel entry below.  The 2D-DWT entries are
+ *     the exception to the first rule: their kernels choose dword and wider
+ *     accesses from the shape, so their three pointers need 16 bytes.
  */
 #ifndef VCF_AMD_H
 #define VCF_AMD_H
@@ -104,7 +116,10 @@ int vcf_dct_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp, 
  * the fused 8x8 kernels, the other supported sizes (vcf_dct_block_size_supported)
  * the generic-B kernels; VCF_DCT_PERCEPTUAL takes any supported B (B != 8
  * through vcf_dct_perceptual_tables' resized tables).  Q >= 1 is the
- * deadzone quantization step (-q). */
+ * deadzone quantization step (-q).  rgb_dev and k_dev need no alignment (the
+ * 8x8 kernels move 8-byte RGB words only when rgb_dev is 8-byte aligned and
+ * 16-byte index chunks only when k_dev is 16-byte aligned, bytes otherwise);
+ * writes the n_frames * Hp * Wp * 3 bytes at k_dev. */
 int vcf_dct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
                       int32_t block_size, int32_t Q, uint32_t flags, uint8_t *k_dev,
                       void *stream);
@@ -112,7 +127,9 @@ int vcf_dct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
 
 
 /* Inverse: n_frames coefficient frames (Hp x Wp x 3) -> RGB frames (H x W x 3),
- * the padding removed.  1 <= Q <= 32767 (the dequantizer works in int16). */
+ * the padding removed.  1 <= Q <= 32767 (the dequantizer works in int16).
+ * k_dev and rgb_dev need no alignment, as for the encode; writes the n_frames *
+ * H * W * 3 bytes at rgb_dev. */
 int vcf_dct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W,
                       int32_t block_size, int32_t Q, uint32_t flags, uint8_t *rgb_dev,
                       void *stream);
@@ -145,14 +162,17 @@ int vcf_mdct_tile_plan(int32_t H, int32_t W, int32_t block_size, uint32_t flags,
  * VCF_DCT_PERCEPTUAL is taken at block_size 8 only, where the reference's
  * cv2.resize of the JPEG tables is the identity; at other sizes it returns
  * VCF_ERR_UNSUPPORTED: cv2 is not available to pin the resized tables.
- * Argument errors are reported before any device work. */
+ * Argument errors are reported before any device work.  The frames need no
+ * alignment (byte loads and stores); writes the n_frames * Hp * Wp * 3 bytes
+ * at k_dev. */
 int vcf_mdct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                        int32_t Q, uint32_t flags, uint8_t *k_dev, void *stream);
 
 /* The inverse, 2D-MDCT.py decode_fn :587-666: coefficient frames -> RGB frames
  * with the padding removed (int16 dequantizer, synthesis columns first, then
  * rows, no boundary extension, * scale, RGB in float32, +128, clip, truncate).
- * Same argument rules as vcf_mdct_dz_encode. */
+ * Same argument rules as vcf_mdct_dz_encode; the frames need no alignment;
+ * writes the n_frames * H * W * 3 bytes at rgb_dev. */
 int vcf_mdct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                        int32_t Q, uint32_t flags, uint8_t *rgb_dev, void *stream);
 
@@ -176,7 +196,9 @@ int vcf_klt_padded_shape(int32_t H, int32_t W, int32_t block_size, int32_t *Hp, 
  * blocks, s = 4 x, x = the YCoCg value after the zero pad and -128 (s is an
  * integer, |s| <= 512).  s1_dev: n_frames x 3 x D, s2_dev: n_frames x 3 x D x
  * D.  Integer arithmetic throughout: the result does not depend on tiling,
- * order or batch.  The covariance is (S2 - S1 S1^T / N) / (16 (N - 1)). */
+ * order or batch.  The covariance is (S2 - S1 S1^T / N) / (16 (N - 1)).
+ * rgb_dev needs no alignment; s1_dev and s2_dev must be 8-byte aligned
+ * (VCF_ERR_INVALID before any device work) and are written whole, nothing else. */
 int vcf_klt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                     int64_t *s1_dev, int64_t *s2_dev, void *stream);
 
@@ -185,14 +207,19 @@ int vcf_klt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t
  * = basis vector k.  Zero pad, -128, YCoCg, coef[k] = sum_j W[k][j] x[j] in
  * float64 (j ascending, FMA), / Q (float64 division), truncated, +128,
  * WRAPPED to u8 (not clipped); subband layout unless VCF_DCT_NO_SUBBANDS (the
- * only flag).  1 <= Q <= 32767.  k_dev: n_frames x Hp x Wp x 3. */
+ * only flag).  1 <= Q <= 32767.  k_dev: n_frames x Hp x Wp x 3, the bytes
+ * written.  The frames need no alignment; weights_f64_dev must be 8-byte
+ * aligned (VCF_ERR_INVALID before any device work). */
 int vcf_klt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const double *weights_f64_dev, uint8_t *k_dev, void *stream);
 
 /* The inverse, 2D-KLT.py decode_fn :738-809: weights_f32_dev is n_frames x 3 x
  * D x D float32 as stored in {out}_weights.npz, widened on the device;
  * rec[j] = sum_k W[k][j] (Q (k - 128)) (int16 dequantizer; k ascending, FMA),
- * inverse YCoCg and +128 in float64, clip, truncate, padding removed. */
+ * inverse YCoCg and +128 in float64, clip, truncate, padding removed.  The
+ * frames need no alignment; weights_f32_dev must be 4-byte aligned
+ * (VCF_ERR_INVALID before any device work); writes the n_frames * H * W * 3
+ * bytes at rgb_dev. */
 int vcf_klt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const float *weights_f32_dev, uint8_t *rgb_dev, void *stream);
 
@@ -220,7 +247,9 @@ int vcf_lbt_tile_plan(int32_t H, int32_t W, int32_t block_size, int32_t decode, 
  * sum of x, s2_dev (n_frames x D x D float64, full symmetric) = sum of x x^T
  * over the 3 N blocks, x = the YCoCg values after the zero pad and -128.
  * Every partial sum is an integer multiple of 1/16 below 2^53: exact, in any
- * order.  Each frame is read once; no float copy of it is written. */
+ * order.  Each frame is read once; no float copy of it is written.  rgb_dev
+ * needs no alignment; s1_dev and s2_dev must be 8-byte aligned (VCF_ERR_INVALID
+ * before any device work) and are written whole, nothing else. */
 int vcf_lbt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                     double *s1_dev, double *s2_dev, void *stream);
 
@@ -241,7 +270,9 @@ int vcf_lbt_train(const double *s1_dev, const double *s2_dev, int64_t n_frames, 
  * ascending), with VCF_DCT_PERCEPTUAL * (QSSs / 121 or 99) as a float64
  * product rounded to float32, / Q (float32), truncated, +128, clipped to
  * 0..255; subband layout unless VCF_DCT_NO_SUBBANDS.  we_dev: n_frames x D x D,
- * mean_dev: n_frames.  k_dev: n_frames x Hp x Wp x 3. */
+ * mean_dev: n_frames.  k_dev: n_frames x Hp x Wp x 3, the bytes written.  The
+ * frames need no alignment; we_dev and mean_dev must be 4-byte aligned
+ * (VCF_ERR_INVALID before any device work). */
 int vcf_lbt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const float *we_dev, const float *mean_dev, uint8_t *k_dev, void *stream);
 
@@ -249,7 +280,9 @@ int vcf_lbt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
  * it is: Q (k - 128) in int16 (with VCF_DCT_PERCEPTUAL divided by the weight
  * in float64 and truncated back into int16), x[j] = sum_k Wd[j][k] y[k]
  * (float32 FMAs, k ascending), + mean, crop, inverse YCoCg and +128 in
- * float32, clip, truncate. */
+ * float32, clip, truncate.  The frames need no alignment; wd_dev and mean_dev
+ * must be 4-byte aligned (VCF_ERR_INVALID before any device work); writes the
+ * n_frames * H * W * 3 bytes at rgb_dev. */
 int vcf_lbt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size, int32_t Q,
                       uint32_t flags, const float *wd_dev, const float *mean_dev, uint8_t *rgb_dev, void *stream);
 
@@ -269,7 +302,8 @@ int vcf_dct_perceptual_tables(int32_t block_size, uint8_t *y_qss, uint8_t *c_qss
 
 /* The generic-B kernels for any supported block size, B = 8 included (tests
  * and A/B checks against the fused 8x8 kernels); same contract as
- * vcf_dct_dz_encode / vcf_dct_dz_decode. */
+ * vcf_dct_dz_encode / vcf_dct_dz_decode, alignment (none needed: byte loads and
+ * stores) and output extent included. */
 int vcf_dct_dz_encode_any(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                           int32_t Q, uint32_t flags, uint8_t *k_dev, void *stream);
 int vcf_dct_dz_decode_any(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
@@ -284,7 +318,10 @@ int vcf_dct_dz_decode_any(const uint8_t *k_dev, int64_t n_frames, int32_t H, int
  *     quantize (:536-545) -> the int32 k array (Hp x Wp x 3 int32);
  *   decode_k32: Q*k in int32 (:561), get_blocks, the IDCT stored into int32,
  *     to_RGB in int32 (no +128), clip, uint8 (:562-568).
- * No VCF_DCT_PERCEPTUAL (the reference refuses -L with -p, :100-105). */
+ * No VCF_DCT_PERCEPTUAL (the reference refuses -L with -p, :100-105).  The u8
+ * frames need no alignment; the int32 k_dev must be 4-byte aligned
+ * (VCF_ERR_INVALID before any device work).  Written: n_frames * Hp * Wp * 3
+ * int32 at k_dev, or n_frames * H * W * 3 bytes at rgb_dev. */
 int vcf_dct_dz_encode_k32(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                           int32_t Q, uint32_t flags, int32_t *k_dev, void *stream);
 int vcf_dct_dz_decode_k32(const int32_t *k_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
@@ -295,7 +332,11 @@ int vcf_dct_dz_decode_k32(const int32_t *k_dev, int64_t n_frames, int32_t H, int
  * colour transform and no +128 on the pixels; the quantizer sees the float32
  * coefficients (subband layout unless -x, -p weights applied, :313-340) and
  * hands back int16 coefficients (:399-410).  Replaces the same spans as
- * vcf_dct_dz_encode/decode minus the deadzone quantizer; any supported B. */
+ * vcf_dct_dz_encode/decode minus the deadzone quantizer; any supported B.  The
+ * u8 frames need no alignment; coef_dev must be aligned to its element, 4
+ * bytes (float, encode) or 2 (int16, decode), else VCF_ERR_INVALID before any
+ * device work.  Written: n_frames * Hp * Wp * 3 floats at coef_dev, or n_frames
+ * * H * W * 3 bytes at rgb_dev. */
 int vcf_dct_raw_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
                        uint32_t flags, float *coef_dev, void *stream);
 int vcf_dct_raw_decode(const int16_t *coef_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
@@ -321,7 +362,11 @@ int vcf_dwt_layout(int32_t H, int32_t W, int32_t levels, int32_t *sub_h, int32_t
  * LH_r, HL_r, HH_r (uint8, h_r x w_r x 3, k + 128 wrapped).  Replaces
  * 2D-DWT.py:57-78 up to the TIFF writer: astype(int16), from_RGB (:62),
  * pywt.wavedec2 mode 'per' per channel (:64), quantize_decom_fn (:67).
- * workspace_dev: n_frames * workspace_bytes_per_frame bytes. */
+ * workspace_dev: n_frames * workspace_bytes_per_frame bytes.  rgb_dev,
+ * packed_dev and workspace_dev must be 16-byte aligned (VCF_ERR_INVALID before
+ * any device work); frames follow at the frame size and the packed size, odd
+ * sizes included (a frame's u16 LL band at an odd address is moved by bytes).
+ * Writes the n_frames * packed_bytes bytes at packed_dev and the workspace. */
 int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                       int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream);
 
@@ -329,7 +374,10 @@ int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
  * (what pywt.waverec2 returns; the reference writes that size too).
  * Replaces 2D-DWT.py:80-101 after the TIFF reader.  1 <= Q <= 32767.
  * Coarsest subbands shorter than filter_length/2 (pywt's short-input code
- * path) run on the separable kernels. */
+ * path) run on the separable kernels.  packed_dev, rgb_dev and workspace_dev
+ * must be 16-byte aligned (VCF_ERR_INVALID before any device work), as for the
+ * encode; writes the n_frames * 2*ceil(H/2) * 2*ceil(W/2) * 3 bytes at rgb_dev
+ * and the workspace. */
 int vcf_dwt_dz_decode(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                       int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream);
 
@@ -357,7 +405,9 @@ int vcf_dwt_plan(int32_t H, int32_t W, int32_t wavelet, int32_t levels, int64_t 
  * workspace, four lifting steps per axis in place of pywt's convolution.
  * NOT bit-exact: every index and decoded byte lies within +-1 of
  * vcf_dwt_dz_encode / _decode's (measured, DESIGN.md §4.5, the lifting form).  No counterpart
- * in the reference -- an extension for callers who accept that tolerance. */
+ * in the reference -- an extension for callers who accept that tolerance.
+ * Alignment (16 bytes for the three pointers) and output extents as for
+ * vcf_dwt_dz_encode / _decode. */
 int vcf_dwt_dz_encode_lift(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                            int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream);
 int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
@@ -384,18 +434,26 @@ int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32
  * one lane per candidate) when bs % 4 == 0 and byte by byte otherwise; the
  * three-step search runs its 8 neighbours in parallel rounds for bs = 16 and
  * one candidate at a time otherwise.  Identical motion fields either way
- * (vcf_ipp_block_match_variant of the A/B library picks per call). */
+ * (vcf_ipp_block_match_variant of the A/B library picks per call).  The frames
+ * and gray_workspace_dev need no alignment (the bs = 16 three-step kernel reads
+ * whole luma words only from a 4-byte aligned workspace); mv_dev must be
+ * 4-byte aligned (VCF_ERR_INVALID before any device work).  Written: the
+ * (H/bs) * (W/bs) * 2 floats at mv_dev and the 2*H*W workspace bytes. */
 int vcf_ipp_block_match(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, int32_t bs,
                         int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream);
 
-/* IPP.motion_compensate (IPP_DCT.py:378-395). */
+/* IPP.motion_compensate (IPP_DCT.py:378-395).  The frames need no alignment;
+ * mv_dev must be 4-byte aligned (VCF_ERR_INVALID before any device work);
+ * writes the H * W * 3 bytes at out_rgb_dev. */
 int vcf_ipp_motion_compensate(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,
                               uint8_t *out_rgb_dev, void *stream);
 
-/* residual_shifted = clip(cur - comp + 128, 0, 255) (IPP_DCT.py:547-551). */
+/* residual_shifted = clip(cur - comp + 128, 0, 255) (IPP_DCT.py:547-551).  No
+ * pointer needs alignment; writes the n bytes at out_dev. */
 int vcf_ipp_residual(const uint8_t *cur_dev, const uint8_t *comp_dev, int64_t n, uint8_t *out_dev, void *stream);
 
-/* recon = clip(comp + rec - 128, 0, 255) (IPP_DCT.py:559-561, 788-790). */
+/* recon = clip(comp + rec - 128, 0, 255) (IPP_DCT.py:559-561, 788-790).  No
+ * pointer needs alignment; writes the n bytes at out_dev. */
 int vcf_ipp_reconstruct(const uint8_t *comp_dev, const uint8_t *rec_dev, int64_t n, uint8_t *out_dev, void *stream);
 
 /* -R block-level RDO of IPP.temporal_filter (IPP_DCT.py:441-536): for every
@@ -405,17 +463,22 @@ int vcf_ipp_reconstruct(const uint8_t *comp_dev, const uint8_t *rec_dev, int64_t
  * mean squared error, get_rate (:265-288) -- and the mode with the smaller
  * D + lambda R (ties to inter).  modes_dev: (H/bs) x (W/bs) u8, 1 = I
  * (intra), 0 = P; costs_dev (NULL or 4 doubles per block): D_inter,
- * R_inter, D_intra, R_intra.  bs in {2, 4, 8, 12, 16, 24, 32}. */
+ * R_inter, D_intra, R_intra.  bs in {2, 4, 8, 12, 16, 24, 32}.  The frames and
+ * modes_dev need no alignment; costs_dev must be 8-byte aligned
+ * (VCF_ERR_INVALID before any device work).  Written: (H/bs) * (W/bs) bytes at
+ * modes_dev and, if given, 4 doubles per block at costs_dev. */
 int vcf_ipp_rdo_modes(const uint8_t *cur_dev, const uint8_t *comp_dev, int32_t H, int32_t W, int32_t bs, int32_t Q,
                       double lambda, uint8_t *modes_dev, double *costs_dev, void *stream);
 
 /* The frame -R hands to the spatial codec (:489-505): P blocks
- * clip(cur - comp + 128), I blocks cur, pixels outside full blocks 128. */
+ * clip(cur - comp + 128), I blocks cur, pixels outside full blocks 128.  No
+ * pointer needs alignment; writes the H * W * 3 bytes at out_dev. */
 int vcf_ipp_rdo_residual(const uint8_t *cur_dev, const uint8_t *comp_dev, const uint8_t *modes_dev, int32_t H,
                          int32_t W, int32_t bs, uint8_t *out_dev, void *stream);
 
 /* Mode-aware reconstruction (:512-526, decoder :770-790): P blocks
- * clip(comp + rec - 128), I blocks rec, pixels outside full blocks 0. */
+ * clip(comp + rec - 128), I blocks rec, pixels outside full blocks 0.  No
+ * pointer needs alignment; writes the H * W * 3 bytes at out_dev. */
 int vcf_ipp_rdo_reconstruct(const uint8_t *comp_dev, const uint8_t *rec_dev, const uint8_t *modes_dev, int32_t H,
                             int32_t W, int32_t bs, uint8_t *out_dev, void *stream);
 
@@ -716,12 +779,16 @@ int vcf_inflate_strips(const uint8_t *comp_dev, const int64_t *comp_off_dev, con
 
 /* k[i] = (int32)(x[i] / Q), truncation toward zero; the division is float32
  * for VCF_DTYPE_F32 input and float64 for every other input type (numpy true
- * division).  Replaces deadzone.CoDec.quantize_fn (deadzone.py:95-102). */
+ * division).  Replaces deadzone.CoDec.quantize_fn (deadzone.py:95-102).  x_dev
+ * must be aligned to its element and k_dev to 4 bytes (VCF_ERR_INVALID before
+ * any device work); writes the n int32 at k_dev. */
 int vcf_deadzone_quantize(const void *x_dev, int32_t x_dtype, int64_t n, int32_t Q, int32_t *k_dev,
                           void *stream);
 
 /* y[i] = Q * k[i] in k's type (VCF_DTYPE_I16 or VCF_DTYPE_I32), wrapping.
- * Replaces deadzone.CoDec.dequantize_fn (deadzone.py:107-117). */
+ * Replaces deadzone.CoDec.dequantize_fn (deadzone.py:107-117).  k_dev and y_dev
+ * must be aligned to the element (VCF_ERR_INVALID before any device work);
+ * writes the n elements at y_dev. */
 int vcf_deadzone_dequantize(const void *k_dev, int32_t k_dtype, int64_t n, int32_t Q, void *y_dev,
                             void *stream);
 
@@ -731,7 +798,11 @@ int vcf_deadzone_dequantize(const void *k_dev, int32_t k_dtype, int64_t n, int32
  * uint8 is assumed (A12; parity unpinned).  n_px pixels of 3 interleaved
  * channels.  Note: 2D-DCT.py / 2D-DWT.py with -t YCrCb still convert with
  * YCoCg (they bind from_RGB/to_RGB from color_transforms.YCoCg, 2D-DCT.py:22-23,
- * 2D-DWT.py:19-20), so they use the YCoCg entry points above. */
+ * 2D-DWT.py:19-20), so they use the YCoCg entry points above.  For these and
+ * the pixel codecs below: u8 pointers need no alignment (words where the
+ * address allows, bytes elsewhere); uint16 and int16 arrays must be 2-byte
+ * aligned (VCF_ERR_INVALID before any device work); the output written is the
+ * n_px * 3 (or n) elements at the output pointer. */
 int vcf_ycrcb_from_rgb(const uint8_t *rgb_dev, int64_t n_px, uint8_t *ycrcb_dev, void *stream);
 int vcf_ycrcb_to_rgb(const uint8_t *ycrcb_dev, int64_t n_px, uint8_t *rgb_dev, void *stream);
 /* YCrCb.encode (:33-51) with -a deadzone: from_RGB, int16, (x / Q) truncated, uint16. */
@@ -772,7 +843,11 @@ int vcf_dz_u8_decode(const uint8_t *k_dev, int64_t n, int32_t Q, uint8_t *y_dev,
 int vcf_lm_levels(int32_t Q_step, int32_t min_val, int32_t max_val);
 int vcf_lm_histogram(const void *x_dev, int32_t x_dtype, int64_t n_px, int32_t channels, int32_t min_val,
                      int32_t max_val, int64_t *counts_dev, void *stream);
-/* Host memory: counts (n_bins, already +1) -> centroids (N doubles); returns N or an error. */
+/* (vcf_lm_histogram, _encode, _decode: x, k and y arrays must be aligned to their
+ * element, counts_dev and centroids_dev to 8 bytes, bad_dev to 4, else
+ * VCF_ERR_INVALID before any device work; written: channels * (max - min + 1)
+ * int64 at counts_dev, n_px * channels elements at k_dev / y_dev.)
+ * Host memory: counts (n_bins, already +1) -> centroids (N doubles); returns N or an error. */
 int vcf_lm_design(const int64_t *counts, int32_t n_bins, int32_t Q_step, int32_t min_val, double *centroids);
 /* centroids_dev: channels x n_levels doubles (channel-major). */
 int vcf_lm_encode(const void *x_dev, int32_t x_dtype, int64_t n_px, int32_t channels, const double *centroids_dev,
@@ -791,7 +866,11 @@ int vcf_lm_decode(const void *k_dev, int32_t k_dtype, int64_t n_px, int32_t chan
  * uint16, centroids K x D float64 (row-major).  Every argument is checked
  * before any device work; the work is enqueued on `stream`.  vcf_vq_init_pp and
  * vcf_vq_fit run host-driven loops: they synchronise `stream` and have finished
- * when they return; the other three only enqueue.
+ * when they return; the other three only enqueue.  For vcf_vq_assign,
+ * _accumulate and _decode: img_dev needs no alignment; labels must be 2-byte,
+ * centroids, distances, sums and counts 8-byte and bad_dev 4-byte aligned
+ * (VCF_ERR_INVALID before any device work); written: N labels (and N
+ * distances), K * D sums and K counts, or the Hl*BS x Wl*BS x C image bytes.
  *
  * vcf_vq_assign: labels[n] = argmin_j dist(n, j), the lowest j on a tie (strict
  * `<` while j ascends), and, when dist_dev is not NULL, that least distance.

@@ -147,3 +147,82 @@ def test_product_path_fails_loudly_without_the_library(tmp_path):
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert p.returncode == 0, p.stderr[-1500:]
     assert p.stdout.startswith("raised") and "no CPU fallback" in p.stdout
+
+
+_A, _M = 0x10000, 0x10001   # a plausible aligned device address, and one a byte off any element's alignment
+
+
+@pytest.mark.parametrize("name,args", [
+    ("vcf_dct_dz_encode_k32", (_A, 1, 8, 8, 4, 7, 0, _M, None)),
+    ("vcf_dct_dz_decode_k32", (_M, 1, 8, 8, 4, 7, 0, _A, None)),
+    ("vcf_dct_raw_encode", (_A, 1, 8, 8, 4, 0, _M, None)),
+    ("vcf_dct_raw_decode", (_M, 1, 8, 8, 4, 0, _A, None)),
+    ("vcf_klt_moments", (_A, 1, 16, 16, 4, _M, _A, None)),
+    ("vcf_klt_moments", (_A, 1, 16, 16, 4, _A, _M, None)),
+    ("vcf_klt_dz_encode", (_A, 1, 16, 16, 4, 32, 0, _M, _A, None)),
+    ("vcf_klt_dz_decode", (_A, 1, 16, 16, 4, 32, 0, _M, _A, None)),
+    ("vcf_lbt_moments", (_A, 1, 16, 16, 8, _M, _A, None)),
+    ("vcf_lbt_moments", (_A, 1, 16, 16, 8, _A, _M, None)),
+    ("vcf_lbt_dz_encode", (_A, 1, 16, 16, 8, 32, 0, _M, _A, _A, None)),
+    ("vcf_lbt_dz_encode", (_A, 1, 16, 16, 8, 32, 0, _A, _M, _A, None)),
+    ("vcf_lbt_dz_decode", (_A, 1, 16, 16, 8, 32, 0, _M, _A, _A, None)),
+    ("vcf_lbt_dz_decode", (_A, 1, 16, 16, 8, 32, 0, _A, _M, _A, None)),
+    ("vcf_ipp_block_match", (_A, _A, 64, 64, 16, 8, 0, _M, _A, None)),
+    ("vcf_ipp_motion_compensate", (_A, _M, 64, 64, 16, _A, None)),
+    ("vcf_ipp_rdo_modes", (_A, _A, 16, 16, 8, 32, 0.5, _A, _M, None)),
+    ("vcf_vq_assign", (_A, 8, 8, 1, 2, _M, 2, _A, None, None)),
+    ("vcf_vq_assign", (_A, 8, 8, 1, 2, _A, 2, _M, None, None)),
+    ("vcf_vq_assign", (_A, 8, 8, 1, 2, _A, 2, _A, _M, None)),
+    ("vcf_vq_accumulate", (_A, 8, 8, 1, 2, _M, 2, _A, _A, None)),
+    ("vcf_vq_accumulate", (_A, 8, 8, 1, 2, _A, 2, _M, _A, None)),
+    ("vcf_vq_accumulate", (_A, 8, 8, 1, 2, _A, 2, _A, _M, None)),
+    ("vcf_vq_decode", (_M, 4, 4, 1, 2, _A, 2, _A, _A, None)),
+    ("vcf_vq_decode", (_A, 4, 4, 1, 2, _M, 2, _A, _A, None)),
+    ("vcf_vq_decode", (_A, 4, 4, 1, 2, _A, 2, _A, _M, None)),
+    ("vcf_ycrcb_dz_encode", (_A, 4, 5, _M, None)),
+    ("vcf_ycrcb_dz_decode", (_M, 4, 5, _A, None)),
+    ("vcf_ycocg_dz_encode", (_A, 4, 5, _M, None)),
+    ("vcf_ycocg_dz_decode", (_M, 4, 5, _A, None)),
+    ("vcf_ycocg_i16_from_rgb", (_A, 4, 0, _M, None)),
+    ("vcf_ycocg_i16_to_rgb", (_M, 4, 0, _A, None)),
+    ("vcf_lm_histogram", (_A, L.VCF_DTYPE_U8, 4, 3, 0, 255, _M, None)),
+    ("vcf_lm_histogram", (_M, L.VCF_DTYPE_I16, 4, 3, 0, 255, _A, None)),
+    ("vcf_lm_encode", (_M, L.VCF_DTYPE_F32, 4, 3, _A, 8, _A, L.VCF_DTYPE_U8, None)),
+    ("vcf_lm_encode", (_A, L.VCF_DTYPE_U8, 4, 3, _M, 8, _A, L.VCF_DTYPE_U8, None)),
+    ("vcf_lm_encode", (_A, L.VCF_DTYPE_U8, 4, 3, _A, 8, _M, L.VCF_DTYPE_U16, None)),
+    ("vcf_lm_decode", (_M, L.VCF_DTYPE_U16, 4, 3, _A, 8, _A, L.VCF_DTYPE_U8, _A, None)),
+    ("vcf_lm_decode", (_A, L.VCF_DTYPE_U8, 4, 3, _A, 8, _M, L.VCF_DTYPE_I16, _A, None)),
+    ("vcf_lm_decode", (_A, L.VCF_DTYPE_U8, 4, 3, _A, 8, _A, L.VCF_DTYPE_U8, _M, None)),
+    ("vcf_deadzone_quantize", (_M, L.VCF_DTYPE_F32, 4, 5, _A, None)),
+    ("vcf_deadzone_quantize", (_A, L.VCF_DTYPE_U8, 4, 5, _M, None)),
+    ("vcf_deadzone_dequantize", (_M, L.VCF_DTYPE_I16, 4, 5, _A, None)),
+    ("vcf_deadzone_dequantize", (_A, L.VCF_DTYPE_I32, 4, 5, _M, None)),
+])
+def test_misaligned_typed_pointer_is_rejected_before_any_device_work(name, args):
+    """A typed pointer off its element's alignment is VCF_ERR_INVALID from the host-side
+    argument check (include/vcf_amd.h, "Alignment and extents"): no HIP call is made, so the
+    made-up addresses are never touched and the check runs without a GPU."""
+    assert getattr(L.lib(), name)(*args) == L.VCF_ERR_INVALID
+    assert b"aligned" in L.lib().vcf_last_error()
+
+
+@pytest.mark.parametrize("name", ["vcf_dwt_dz_encode", "vcf_dwt_dz_decode", "vcf_dwt_dz_encode_lift",
+                                  "vcf_dwt_dz_decode_lift"])
+@pytest.mark.parametrize("which", [0, 7, 8])
+def test_dwt_pointers_need_16_bytes(name, which):
+    """The 2D-DWT entries take rgb_dev, packed_dev and workspace_dev at 16-byte alignment only
+    (include/vcf_amd.h); 8 bytes off is rejected like 1 byte off, before any device work."""
+    wi = ctypes.c_int32()
+    assert L.lib().vcf_wavelet_index(b"bior4.4", ctypes.byref(wi)) == 0
+    for off in (1, 8):
+        a = [_A, 1, 24, 32, wi.value, 2, 32, _A, _A, None]
+        a[which] = _A + off
+        assert getattr(L.lib(), name)(*a) == L.VCF_ERR_INVALID
+        assert b"aligned" in L.lib().vcf_last_error()
+
+
+def test_unknown_dtype_is_reported_before_alignment():
+    assert L.lib().vcf_deadzone_quantize(_M, 99, 4, 5, _A, None) == L.VCF_ERR_INVALID
+    assert b"dtype" in L.lib().vcf_last_error()
+    assert L.lib().vcf_deadzone_dequantize(_M, L.VCF_DTYPE_U8, 4, 5, _A, None) == L.VCF_ERR_INVALID
+    assert b"dtype" in L.lib().vcf_last_error()

@@ -739,6 +739,11 @@ int check_any(const void *a, const void *b, int64_t n_frames, int H, int W, int 
 {
     const bool k32 = mode == kK32;
     if (!a || !b) return set_error(VCF_ERR_INVALID, "null buffer");
+    // the coefficient array is the typed pointer: int32 (k32), float out / int16 in (raw); the u8
+    // frames on either side are read and written byte by byte
+    const void *coef_dev = decode ? a : b;
+    if (k32 || (mode == kRaw && !decode)) VCF_REQUIRE_ALIGNED(coef_dev, 4);
+    else if (mode == kRaw) VCF_REQUIRE_ALIGNED(coef_dev, 2);
     if (n_frames < 0) return set_error(VCF_ERR_INVALID, "n_frames < 0");
     if (H <= 0 || W <= 0)
         return set_error(VCF_ERR_INVALID, "Input image must be a 3D array (height, width, channels).");

@@ -639,7 +639,10 @@ int launch_decode_cols(const uint8_t *k_dev, int64_t n_frames, uint8_t *rgb_dev,
     return VCF_OK;
 }
 
-void make_geom(int32_t H, int32_t W, Geom &g)
+// k_dev = the call's coefficient frames: the 16-byte copies of move_runs_tab / move_runs_full and of
+// the decode's staging loop run at k_dev + multiples of 16, so they also need the pointer's low
+// four bits clear.  An aligned pointer leaves every field as the shape alone gives it.
+void make_geom(int32_t H, int32_t W, const uint8_t *k_dev, Geom &g)
 {
     g.H = H;
     g.W = W;
@@ -656,7 +659,15 @@ void make_geom(int32_t H, int32_t W, Geom &g)
     g.out_stride = (long long)g.Hp * g.Wp * 3;
     // every subband run starts 16-B aligned and spans whole 16-B chunks iff
     // nbx % 16 == 0 (then Wp*3, nbx*3, 768 and the frame size are multiples of 16)
-    g.vec = (g.nbx % 16 == 0) ? 1 : 0;
+    g.vec = (g.nbx % 16 == 0 && aligned_to(k_dev, 16)) ? 1 : 0;
+}
+
+// The PAD = false instantiations move a block row's 24 RGB bytes as three 8-byte words
+// (load_block, the decode epilogues); an RGB pointer off 8 bytes takes the PAD = true ones, whose
+// byte loads and stores are as valid with top = left = 0.
+bool rgb_needs_bytes(const Geom &g, const uint8_t *rgb_dev)
+{
+    return g.Hp != g.H || g.Wp != g.W || !aligned_to(rgb_dev, 8);
 }
 
 int check_args(const void *a, const void *b, int64_t n_frames, int32_t H, int32_t W,
@@ -707,11 +718,11 @@ int vcf_dct_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
     if (rc != VCF_OK) return rc;
     if (n_frames == 0) return VCF_OK;
     Geom g;
-    make_geom(H, W, g);
+    make_geom(H, W, k_dev, g);
     const bool pow2 = (Q & (Q - 1)) == 0;
     const bool sub = !(flags & VCF_DCT_NO_SUBBANDS);
     const bool perc = (flags & VCF_DCT_PERCEPTUAL) != 0;
-    const bool pad = (g.Hp != H) || (g.Wp != W);
+    const bool pad = rgb_needs_bytes(g, rgb_dev);
     EncConsts K;
     make_enc_consts(K, Q);
     const FinalK rowk = pow2 ? row_final_k(Q) : final_k(1.0f, 1.0f);
@@ -748,10 +759,10 @@ int vcf_dct_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t
     if (rc != VCF_OK) return rc;
     if (n_frames == 0) return VCF_OK;
     Geom g;
-    make_geom(H, W, g);
+    make_geom(H, W, k_dev, g);
     const bool sub = !(flags & VCF_DCT_NO_SUBBANDS);
     const bool perc = (flags & VCF_DCT_PERCEPTUAL) != 0;
-    const bool pad = (g.Hp != H) || (g.Wp != W);
+    const bool pad = rgb_needs_bytes(g, rgb_dev);
     return launch_decode_cols<32>(k_dev, n_frames, rgb_dev, g, (int)Q, sub, perc, pad, stream);
 }
 

@@ -940,7 +940,7 @@ __global__ __launch_bounds__(192) void dwt_strip_kernel(const uint8_t *__restric
         __builtin_amdgcn_raw_buffer_store_b8(q8(src ? lo : hi), rs_pk, ((uint32_t)off_r1 + e) | drop1, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b8(q8(hi), rs_pk, ((uint32_t)off_hh + e) | drop_d, 0, 0);
         if (LAST)
-            __builtin_amdgcn_raw_buffer_store_b16(q16(lo), rs_pk, ((uint32_t)ll_off + 2 * e) | drop_a, 0, 0);
+            buffer_store_u16_le(q16(lo), rs_pk, pk, ((uint32_t)ll_off + 2 * e) | drop_a);
         else
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U32x2, lo), rs_ll,
                                                   (uint32_t)(((long long)o * hw + ocg) * 8) | drop_a, 0, 0);
@@ -1285,6 +1285,13 @@ int check_dwt(const void *a, const void *b, int64_t n_frames, int32_t H, int32_t
     if (Q < 1 || (decode && Q > 32767)) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if ((long long)H * W * 3 >= (1LL << 31)) return set_error(VCF_ERR_INVALID, "frame too large");
     if (n_frames > 0 && (!a || !b)) return set_error(VCF_ERR_INVALID, "null buffer");
+    // The level kernels choose their dword, 8- and 16-byte accesses to the frames and to the packed
+    // subbands from the shape and from offsets within the call's buffers, some also from the address
+    // (vcf_dwt.hip copy-out, vcf_idwt_line.h, vcf_idwt_band21.h), the lifting ones from the shape
+    // alone: a base that is 16-byte aligned gives every access of up to 16 bytes the alignment it
+    // has with an allocation's base, so that is the contract (include/vcf_amd.h).
+    VCF_REQUIRE_ALIGNED(a, 16);
+    VCF_REQUIRE_ALIGNED(b, 16);
     return VCF_OK;
 }
 
@@ -1951,6 +1958,7 @@ static int dwt_encode(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_f
     if (rc != VCF_OK) return rc;
     if (n_frames == 0) return VCF_OK;
     if (!workspace_dev) return set_error(VCF_ERR_INVALID, "null workspace");
+    VCF_REQUIRE_ALIGNED(workspace_dev, 16);
     if (n_frames * 3 > 65535) return set_error(VCF_ERR_INVALID, "at most 21845 frames per call");
     hipStream_t s = (hipStream_t)stream;
     DwtGeom g;
@@ -2029,6 +2037,7 @@ static int dwt_decode(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t 
     if (rc != VCF_OK) return rc;
     if (n_frames == 0) return VCF_OK;
     if (!workspace_dev) return set_error(VCF_ERR_INVALID, "null workspace");
+    VCF_REQUIRE_ALIGNED(workspace_dev, 16);
     if (n_frames * 3 > 65535) return set_error(VCF_ERR_INVALID, "at most 21845 frames per call");
     hipStream_t s = (hipStream_t)stream;
     Filters flt;
@@ -2089,6 +2098,7 @@ static int dwt_encode_lift(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_
     if (rc != VCF_OK || (rc = lift_check(wavelet)) != VCF_OK) return rc;
     if (n_frames == 0) return VCF_OK;
     if (!workspace_dev) return set_error(VCF_ERR_INVALID, "null workspace");
+    VCF_REQUIRE_ALIGNED(workspace_dev, 16);
     hipStream_t s = (hipStream_t)stream;
     DwtGeom g;
     dwt_geom(H, W, levels, 10, g);
@@ -2216,6 +2226,7 @@ static int dwt_decode_lift(const DwtSchedule &sc, const uint8_t *packed_dev, int
     if (rc != VCF_OK || (rc = lift_check(wavelet)) != VCF_OK) return rc;
     if (n_frames == 0) return VCF_OK;
     if (!workspace_dev) return set_error(VCF_ERR_INVALID, "null workspace");
+    VCF_REQUIRE_ALIGNED(workspace_dev, 16);
     hipStream_t s = (hipStream_t)stream;
     DwtGeom g;
     dwt_geom(H, W, levels, 10, g);

@@ -339,8 +339,8 @@ __global__ __launch_bounds__(kBNT, 2) void dwt_band12_kernel(
                 __builtin_amdgcn_raw_buffer_store_b8(q8(hi), rs_pk, ((uint32_t)o2hh + e) | (src2 ? drop2 : kDrop), 0,
                                                      0);
                 if constexpr (LAST2)
-                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(uint32_t)(kq(lo) + 128), rs_pk,
-                                                          ((uint32_t)ll_off + 2 * e) | drop2a, 0, 0);
+                    buffer_store_u16_le((uint16_t)(uint32_t)(kq(lo) + 128), rs_pk, pk,
+                                        ((uint32_t)ll_off + 2 * e) | drop2a);
                 else
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U32x2, lo), rs_ll, ell | drop2a, 0, 0);
             }

@@ -351,8 +351,8 @@ __device__ __forceinline__ void lift_fwd_body(const uint8_t *__restrict__ rgb, l
             q[2][k] = (uint8_t)(uint32_t)(qk<QP2>(hhv[k], Q, qsh) + 128);
             const uint32_t o = (uint32_t)(orow + jl + k);          // (a halo lane's may be junk: dropped)
             if (LAST)
-                __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(uint32_t)(qk<QP2>(ll[k], Q, qsh) + 128), rs_pk,
-                                                      ((uint32_t)ll_off + 2 * (3 * o + ch)) | drop[k], 0, 0);
+                buffer_store_u16_le((uint16_t)(uint32_t)(qk<QP2>(ll[k], Q, qsh) + 128), rs_pk, pk,
+                                    ((uint32_t)ll_off + 2 * (3 * o + ch)) | drop[k]);
             else if (EDGE)
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U32x2, ll[k]), rs_ll, (8 * o) | drop[k], 0,
                                                       0);
@@ -499,7 +499,7 @@ __device__ __forceinline__ void lift_inv_body(const uint8_t *__restrict__ packed
 #pragma unroll
         for (int k = 0; k < kP; ++k) {
             const long long idx = row + j[k];
-            if (FROM_PACKED) nA[k] = dequant((int16_t)*(const uint16_t *)(pk + ll_off + 2 * (3 * idx + ch)), Q);
+            if (FROM_PACKED) nA[k] = dequant((int16_t)load_u16_le(pk + ll_off + 2 * (3 * idx + ch)), Q);
             else if (EDGE) nA[k] = src[(long long)qf * lda + j[k]];
             nb[0][k] = pk[off_hl + 3 * idx + ch];
             nb[1][k] = pk[off_lh + 3 * idx + ch];
@@ -838,8 +838,8 @@ __global__ __launch_bounds__(kNT) void lift_fwd12_kernel(const uint8_t *__restri
         const uint32_t d2 = m2 >= M0 ? drop2 : kDrop;          // level-2 row m2 once the pipeline is full
         const uint32_t o2 = (uint32_t)(m2 * hw2 + j2);
         if (LAST2)
-            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(uint32_t)(qk<QP2>(L2[0], Q, qsh) + 128), rs_pk,
-                                                  ((uint32_t)ll_off + 2 * (3 * o2 + ch)) | d2, 0, 0);
+            buffer_store_u16_le((uint16_t)(uint32_t)(qk<QP2>(L2[0], Q, qsh) + 128), rs_pk, pk,
+                                ((uint32_t)ll_off + 2 * (3 * o2 + ch)) | d2);
         else
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(U32x2, L2[0]), rs_ll, (8 * o2) | d2, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(uint32_t)(qk<QP2>(D2[0], Q, qsh) + 128), rs_pk,
@@ -916,7 +916,7 @@ __global__ __launch_bounds__(kNT) void lift_inv21_kernel(const uint8_t *__restri
     int n2[3], n1[2][3][2];
     auto load2 = [&]() {
         const long long idx = (long long)q2f * w2 + j2;
-        nA2 = FROM_PACKED2 ? dequant((int16_t)*(const uint16_t *)(pk + ll_off + 2 * (3 * idx + ch)), Q)
+        nA2 = FROM_PACKED2 ? dequant((int16_t)load_u16_le(pk + ll_off + 2 * (3 * idx + ch)), Q)
                            : src[(long long)q2f * w2 + j2];
         n2[0] = pk[off2_hl + 3 * idx + ch];
         n2[1] = pk[off2_lh + 3 * idx + ch];

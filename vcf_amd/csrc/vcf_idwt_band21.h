@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kB21NT) void idwt_band21_kernel(
     auto load2 = [&](int y) -> Row2 {   // level-2 row y (already wrapped)
         const long long rb = (long long)y * w2 * 3;
         Row2 v;
-        if (FROM_PACKED_LL2) v.ll = dequant((int16_t)*reinterpret_cast<const uint16_t *>(pk + ll_off + 2 * (rb + b2)), Q);
+        if (FROM_PACKED_LL2) v.ll = dequant((int16_t)load_u16_le(pk + ll_off + 2 * (rb + b2)), Q);
         else v.ll = (pv + (long long)y * lda)[c2];
         const uint8_t *row = pk + rb;
         v.hl = (row + off2_hl)[b2];

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kINT) void idwt_line_kernel(const uint8_t *__restri
         const long long rb = (long long)y * w * 3;
         const uint8_t *row = pk + rb;
         if (FROM_PACKED_LL) {
-            const uint16_t v = *reinterpret_cast<const uint16_t *>(pk + ll_off + 2 * (rb + bo));
+            const uint16_t v = load_u16_le(pk + ll_off + 2 * (rb + bo));
             c.ll = dequant((int16_t)v, Q);
         } else {
             c.ll = (pv + (long long)y * lda)[x];

@@ -9,6 +9,38 @@ namespace vcf {
 int set_error(int code, const char *fmt, ...);
 int hip_check(hipError_t e, const char *what);
 
+// Pointer alignment (include/vcf_amd.h, "Alignment and extents"): byte-typed frames need none, so an
+// entry point takes its vector path only where aligned_to() allows it; a typed pointer off its
+// element's alignment is an argument error (VCF_ERR_INVALID before any device work).
+inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// A little-endian u16 inside a byte-typed buffer (the packed LL band of the 2D-DWT): one 16-bit
+// access at an even address, two bytes at an odd one -- a frame of a batch starts at an odd address
+// whenever the packed frame size is odd.  Device code only.  The buffer form keeps the callers' dropped stores dropped:
+// an offset with bit 31 set stays past the buffer at offset + 1.
+#if defined(__HIP__)
+__device__ __forceinline__ uint16_t load_u16_le(const uint8_t *p)
+{
+    if ((reinterpret_cast<uintptr_t>(p) & 1) == 0) return *reinterpret_cast<const uint16_t *>(p);
+    return (uint16_t)(p[0] | (p[1] << 8));
+}
+__device__ __forceinline__ void buffer_store_u16_le(uint16_t v, __amdgpu_buffer_rsrc_t rs, const uint8_t *base,
+                                                    uint32_t off)
+{
+    if (((reinterpret_cast<uintptr_t>(base) + off) & 1) == 0) {
+        __builtin_amdgcn_raw_buffer_store_b16(v, rs, off, 0, 0);
+    } else {
+        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, rs, off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(v >> 8), rs, off + 1, 0, 0);
+    }
+}
+#endif
+#define VCF_REQUIRE_ALIGNED(p, a)                                                                    \
+    do {                                                                                             \
+        if ((p) && !vcf::aligned_to((p), (a)))                                                       \
+            return vcf::set_error(VCF_ERR_INVALID, #p " must be %d-byte aligned", (int)(a));         \
+    } while (0)
+
 // A batch whose frames are a grid's y or z dimension, in launches of at most 65535 of them (the
 // dimension's limit): launch(f0, nf) enqueues frames f0 .. f0 + nf - 1, `what` names it in the
 // error.  Returns the first launch's error, or 0.

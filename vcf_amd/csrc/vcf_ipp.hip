@@ -272,8 +272,10 @@ __global__ __launch_bounds__(64) void ipp_tss16_kernel(const uint8_t *__restrict
     const int i = by * 16, j = bx * 16;
     const int wy0 = i - kTssR, wx0 = j - kTssR;      // frame position of window (0, 0)
     // whole words straight from the frame when the window lies inside it and
-    // rows are word aligned (W % 4 == 0; wx0 is a multiple of 16); else bytes
-    const bool words = (W & 3) == 0 && wx0 >= 0 && wx0 + 4 * kTssWP <= W && wy0 >= 0 && wy0 + kTssWS <= H;
+    // rows are word aligned (W % 4 == 0; wx0 is a multiple of 16; the luma plane
+    // itself, which is the caller's gray workspace at any byte address); else bytes
+    const bool words = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(ref) & 3) == 0 && wx0 >= 0 &&
+                       wx0 + 4 * kTssWP <= W && wy0 >= 0 && wy0 + kTssWS <= H;
     for (int t = lane; t < kTssWS * kTssWP; t += 64) {
         const int r = t / kTssWP, q = t - r * kTssWP;
         const int y = wy0 + r;
@@ -436,6 +438,7 @@ int ipp_block_match(int32_t variant, const uint8_t *ref_rgb_dev, const uint8_t *
                     int32_t bs, int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream)
 {
     if (!ref_rgb_dev || !cur_rgb_dev || !mv_dev || !gray_workspace_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(mv_dev, 4);
     if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad frame shape");
     if (bs < 1 || bs > kMaxBs) return set_error(VCF_ERR_UNSUPPORTED, "block size %d (1..%d)", bs, kMaxBs);
     if (sr < 0 || sr > kMaxSr) return set_error(VCF_ERR_UNSUPPORTED, "search range %d (0..%d)", sr, kMaxSr);
@@ -483,6 +486,7 @@ int vcf_ipp_motion_compensate(const uint8_t *ref_rgb_dev, const float *mv_dev, i
                               uint8_t *out_rgb_dev, void *stream)
 {
     if (!ref_rgb_dev || !mv_dev || !out_rgb_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(mv_dev, 4);
     if (H <= 0 || W <= 0 || bs < 1) return set_error(VCF_ERR_INVALID, "bad arguments");
     const long long npx = (long long)H * W;
     hipLaunchKernelGGL(ipp_mc_kernel, dim3(blocks_for(npx)), dim3(256), 0, (hipStream_t)stream, ref_rgb_dev, mv_dev,

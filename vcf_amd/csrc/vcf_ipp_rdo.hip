@@ -250,6 +250,7 @@ int vcf_ipp_rdo_modes(const uint8_t *cur_dev, const uint8_t *comp_dev, int32_t H
 {
     int rc = check_frame(cur_dev, comp_dev, modes_dev, H, W, bs);
     if (rc != VCF_OK) return rc;
+    VCF_REQUIRE_ALIGNED(costs_dev, 8);
     if (Q < 1) return set_error(VCF_ERR_INVALID, "quantization step %d", Q);
     if (H / bs == 0 || W / bs == 0) return VCF_OK;   // no full block: empty mode map
     rc = ensure_tables();

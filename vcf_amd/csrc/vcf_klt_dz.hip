@@ -327,6 +327,8 @@ int vcf_klt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t
     BlockGeom g;
     int rc = check_args(rgb_dev, s1_dev, s2_dev, n_frames, H, W, block_size, 1, 0, g);
     if (rc != VCF_OK) return rc;
+    VCF_REQUIRE_ALIGNED(s1_dev, 8);
+    VCF_REQUIRE_ALIGNED(s2_dev, 8);
     const long long D = g.D;
     rc = hip_check(hipMemsetAsync(s1_dev, 0, (size_t)(n_frames * 3 * D * 8), (hipStream_t)stream), "hipMemsetAsync(S1)");
     if (rc != VCF_OK) return rc;
@@ -347,6 +349,7 @@ int vcf_klt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
     BlockGeom g;
     const int rc = check_args(rgb_dev, weights_f64_dev, k_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
+    VCF_REQUIRE_ALIGNED(weights_f64_dev, 8);
     const BlockPlan p = make_block_plan(g, false, 2);
     if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;
@@ -366,6 +369,7 @@ int vcf_klt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t
     BlockGeom g;
     const int rc = check_args(k_dev, weights_f32_dev, rgb_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
+    VCF_REQUIRE_ALIGNED(weights_f32_dev, 4);
     const BlockPlan p = make_block_plan(g, true, 2);
     if (p.cls < 0) return set_error(VCF_ERR_UNSUPPORTED, "block size %d: tile does not fit the LDS", block_size);
     const int sub = (flags & VCF_DCT_NO_SUBBANDS) ? 0 : 1;

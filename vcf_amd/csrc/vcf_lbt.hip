@@ -444,6 +444,8 @@ int vcf_lbt_moments(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t
     BlockGeom g;
     int rc = check_args(rgb_dev, s1_dev, s2_dev, n_frames, H, W, block_size, 1, 0, g);
     if (rc != VCF_OK) return rc;
+    VCF_REQUIRE_ALIGNED(s1_dev, 8);
+    VCF_REQUIRE_ALIGNED(s2_dev, 8);
     const long long D = g.D;
     rc = hip_check(hipMemsetAsync(s1_dev, 0, (size_t)(n_frames * D * 8), (hipStream_t)stream), "hipMemsetAsync(S1)");
     if (rc != VCF_OK) return rc;
@@ -483,6 +485,8 @@ int vcf_lbt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32
     int rc = check_args(rgb_dev, we_dev, k_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
     if (!mean_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(we_dev, 4);
+    VCF_REQUIRE_ALIGNED(mean_dev, 4);
     LbtScale pq;
     rc = make_scale(block_size, flags, pq);
     if (rc != VCF_OK) return rc;
@@ -506,6 +510,8 @@ int vcf_lbt_dz_decode(const uint8_t *k_dev, int64_t n_frames, int32_t H, int32_t
     int rc = check_args(k_dev, wd_dev, rgb_dev, n_frames, H, W, block_size, Q, flags, g);
     if (rc != VCF_OK) return rc;
     if (!mean_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(wd_dev, 4);
+    VCF_REQUIRE_ALIGNED(mean_dev, 4);
     LbtScale pq;
     rc = make_scale(block_size, flags, pq);
     if (rc != VCF_OK) return rc;

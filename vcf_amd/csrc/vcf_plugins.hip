@@ -360,6 +360,12 @@ int dispatch_dtype(int dt, F &&f)
     }
 }
 
+// element size of a dispatch_dtype type (1 for one it rejects: the dispatch reports that)
+uintptr_t dtype_align(int dt)
+{
+    return dt == VCF_DTYPE_F32 ? 4 : (dt == VCF_DTYPE_I16 || dt == VCF_DTYPE_U16) ? 2 : 1;
+}
+
 int check_range(int lo, int hi)
 {
     if (hi < lo) return set_error(VCF_ERR_INVALID, "max must be larger than min in range parameter.");
@@ -470,6 +476,7 @@ int vcf_ycrcb_dz_encode(const uint8_t *rgb_dev, int64_t n_px, int32_t Q, uint16_
     if (Q < 1) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if (n_px == 0) return VCF_OK;
     if (!rgb_dev || !k_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(k_dev, 2);
     hipLaunchKernelGGL(ycrcb_dz_encode_kernel, dim3(grid_for(n_px)), dim3(kThreads), 0, (hipStream_t)stream, rgb_dev,
                        n_px, Q, k_dev);
     return hip_check(hipGetLastError(), "ycrcb_dz_encode_kernel launch");
@@ -481,6 +488,7 @@ int vcf_ycrcb_dz_decode(const uint16_t *k_dev, int64_t n_px, int32_t Q, uint8_t 
     if (Q < 1) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if (n_px == 0) return VCF_OK;
     if (!rgb_dev || !k_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(k_dev, 2);
     hipLaunchKernelGGL(ycrcb_dz_decode_kernel, dim3(grid_for(n_px)), dim3(kThreads), 0, (hipStream_t)stream, k_dev,
                        n_px, Q, rgb_dev);
     return hip_check(hipGetLastError(), "ycrcb_dz_decode_kernel launch");
@@ -492,6 +500,7 @@ int vcf_ycocg_dz_encode(const uint8_t *rgb_dev, int64_t n_px, int32_t Q, uint16_
     if (Q < 1) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if (n_px == 0) return VCF_OK;
     if (!rgb_dev || !k_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(k_dev, 2);
     hipLaunchKernelGGL(ycocg_dz_encode_kernel, dim3(grid_for(n_px, 16)), dim3(kThreads), 0, (hipStream_t)stream,
                        rgb_dev, n_px, Q, k_dev);
     return hip_check(hipGetLastError(), "ycocg_dz_encode_kernel launch");
@@ -504,6 +513,7 @@ int vcf_ycocg_dz_decode(const uint16_t *k_dev, int64_t n_px, int32_t Q, uint8_t 
         return set_error(VCF_ERR_UNSUPPORTED, "quantization step %d: int16 dequantization needs 1 <= Q <= 32767", Q);
     if (n_px == 0) return VCF_OK;
     if (!rgb_dev || !k_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(k_dev, 2);
     hipLaunchKernelGGL(ycocg_dz_decode_kernel, dim3(grid_for(n_px)), dim3(kThreads), 0, (hipStream_t)stream, k_dev,
                        n_px, Q, rgb_dev);
     return hip_check(hipGetLastError(), "ycocg_dz_decode_kernel launch");
@@ -514,6 +524,7 @@ int vcf_ycocg_i16_from_rgb(const uint8_t *rgb_dev, int64_t n_px, int32_t offset0
     if (n_px < 0) return set_error(VCF_ERR_INVALID, "n_px < 0");
     if (n_px == 0) return VCF_OK;
     if (!rgb_dev || !out_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(out_dev, 2);
     hipLaunchKernelGGL(ycocg_i16_from_rgb_kernel, dim3(grid_for(n_px)), dim3(kThreads), 0, (hipStream_t)stream,
                        rgb_dev, n_px, offset0, out_dev);
     return hip_check(hipGetLastError(), "ycocg_i16_from_rgb_kernel launch");
@@ -524,6 +535,7 @@ int vcf_ycocg_i16_to_rgb(const int16_t *in_dev, int64_t n_px, int32_t offset0, u
     if (n_px < 0) return set_error(VCF_ERR_INVALID, "n_px < 0");
     if (n_px == 0) return VCF_OK;
     if (!rgb_dev || !in_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(in_dev, 2);
     hipLaunchKernelGGL(ycocg_i16_to_rgb_kernel, dim3(grid_for(n_px)), dim3(kThreads), 0, (hipStream_t)stream, in_dev,
                        n_px, offset0, rgb_dev);
     return hip_check(hipGetLastError(), "ycocg_i16_to_rgb_kernel launch");
@@ -568,6 +580,8 @@ int vcf_lm_histogram(const void *x_dev, int32_t x_dtype, int64_t n_px, int32_t c
     if (rc != VCF_OK) return rc;
     if (n_px < 0 || channels < 1) return set_error(VCF_ERR_INVALID, "bad shape");
     if (!counts_dev || (n_px && !x_dev)) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(counts_dev, 8);
+    VCF_REQUIRE_ALIGNED(x_dev, dtype_align(x_dtype));
     const hipStream_t s = (hipStream_t)stream;
     const int64_t nb = (int64_t)max_val - min_val + 1;
     rc = hip_check(hipMemsetAsync(counts_dev, 0, (size_t)(channels * nb) * sizeof(int64_t), s), "hipMemsetAsync");
@@ -618,6 +632,9 @@ int vcf_lm_encode(const void *x_dev, int32_t x_dtype, int64_t n_px, int32_t chan
     if (n_px < 0 || channels < 1 || n_levels < 1) return set_error(VCF_ERR_INVALID, "bad shape");
     if (n_px == 0) return VCF_OK;
     if (!x_dev || !k_dev || !centroids_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(x_dev, dtype_align(x_dtype));
+    VCF_REQUIRE_ALIGNED(k_dev, dtype_align(k_dtype));
+    VCF_REQUIRE_ALIGNED(centroids_dev, 8);
     const int64_t n = n_px * channels;
     const hipStream_t s = (hipStream_t)stream;
     return dispatch_dtype(x_dtype, [&](auto *ti) -> int {
@@ -637,6 +654,10 @@ int vcf_lm_decode(const void *k_dev, int32_t k_dtype, int64_t n_px, int32_t chan
         return set_error(VCF_ERR_INVALID, "indices and levels are stored in integer arrays");
     if (n_px == 0) return VCF_OK;
     if (!k_dev || !y_dev || !centroids_dev || !bad_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(k_dev, dtype_align(k_dtype));
+    VCF_REQUIRE_ALIGNED(y_dev, dtype_align(y_dtype));
+    VCF_REQUIRE_ALIGNED(centroids_dev, 8);
+    VCF_REQUIRE_ALIGNED(bad_dev, 4);
     const int64_t n = n_px * channels;
     const hipStream_t s = (hipStream_t)stream;
     return dispatch_dtype(k_dtype, [&](auto *ti) -> int {

@@ -69,6 +69,11 @@ int vcf_deadzone_quantize(const void *x_dev, int32_t x_dtype, int64_t n, int32_t
     if (Q < 1) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if (n == 0) return VCF_OK;
     if (!x_dev || !k_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    if (x_dtype != VCF_DTYPE_F32 && x_dtype != VCF_DTYPE_F64 && x_dtype != VCF_DTYPE_I16 && x_dtype != VCF_DTYPE_I32 &&
+        x_dtype != VCF_DTYPE_U8)
+        return set_error(VCF_ERR_INVALID, "unsupported input dtype %d", x_dtype);
+    VCF_REQUIRE_ALIGNED(k_dev, 4);
+    VCF_REQUIRE_ALIGNED(x_dev, x_dtype == VCF_DTYPE_F64 ? 8 : x_dtype == VCF_DTYPE_I16 ? 2 : x_dtype == VCF_DTYPE_U8 ? 1 : 4);
     const dim3 grid(grid_for(n)), block(256);
     hipStream_t s = (hipStream_t)stream;
     switch (x_dtype) {
@@ -100,6 +105,10 @@ int vcf_deadzone_dequantize(const void *k_dev, int32_t k_dtype, int64_t n, int32
     if (Q < 1) return set_error(VCF_ERR_INVALID, "quantization step %d out of range", Q);
     if (n == 0) return VCF_OK;
     if (!k_dev || !y_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    if (k_dtype != VCF_DTYPE_I16 && k_dtype != VCF_DTYPE_I32)
+        return set_error(VCF_ERR_INVALID, "unsupported index dtype %d", k_dtype);
+    VCF_REQUIRE_ALIGNED(k_dev, k_dtype == VCF_DTYPE_I16 ? 2 : 4);
+    VCF_REQUIRE_ALIGNED(y_dev, k_dtype == VCF_DTYPE_I16 ? 2 : 4);
     const dim3 grid(grid_for(n)), block(256);
     hipStream_t s = (hipStream_t)stream;
     switch (k_dtype) {

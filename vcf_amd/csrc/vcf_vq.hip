@@ -552,6 +552,9 @@ int vcf_vq_assign(const uint8_t *img_dev, int32_t H, int32_t W, int32_t C, int32
     int rc;
     if ((rc = make_geo(H, W, C, block_size, &g)) || (rc = check_k(g, K))) return rc;
     if (!img_dev || !centroids_dev || !labels_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(centroids_dev, 8);
+    VCF_REQUIRE_ALIGNED(labels_dev, 2);
+    VCF_REQUIRE_ALIGNED(dist_dev, 8);
     return launch_assign(img_dev, g, centroids_dev, K, labels_dev, dist_dev, nullptr, (hipStream_t)stream);
 }
 
@@ -562,6 +565,9 @@ int vcf_vq_accumulate(const uint8_t *img_dev, int32_t H, int32_t W, int32_t C, i
     int rc;
     if ((rc = make_geo(H, W, C, block_size, &g)) || (rc = check_k(g, K))) return rc;
     if (!img_dev || !labels_dev || !sums_dev || !counts_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(labels_dev, 2);
+    VCF_REQUIRE_ALIGNED(sums_dev, 8);
+    VCF_REQUIRE_ALIGNED(counts_dev, 8);
     return launch_accumulate(img_dev, g, labels_dev, K, sums_dev, counts_dev, (hipStream_t)stream);
 }
 
@@ -717,6 +723,9 @@ int vcf_vq_decode(const uint16_t *labels_dev, int32_t Hl, int32_t Wl, int32_t C,
     if ((rc = make_geo(Hl * block_size, Wl * block_size, C, block_size, &g))) return rc;
     if (K < 1 || K > kMaxK) return set_error(VCF_ERR_INVALID, "1 <= K <= %d (got %d)", kMaxK, K);
     if (!labels_dev || !centroids_dev || !img_dev || !bad_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(labels_dev, 2);
+    VCF_REQUIRE_ALIGNED(centroids_dev, 8);
+    VCF_REQUIRE_ALIGNED(bad_dev, 4);
     const int64_t n = (int64_t)g.H * g.pitch;
     hipLaunchKernelGGL(vq_decode_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, labels_dev, g, centroids_dev, K, img_dev, bad_dev);
