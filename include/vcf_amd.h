@@ -1011,6 +1011,31 @@ int vcf_ssim_u8(const uint8_t *a_dev, const uint8_t *b_dev, int64_t n_frames, in
 /* The edge, in windows, of the square tile one workgroup of vcf_ssim_u8 takes (for tests and benchmarks). */
 int vcf_ssim_tile(void);
 
+/* ---- histograms of index planes (the rate estimate of vcf_amd/rate.py) -----------
+ *
+ * idx_dev holds n_frames contiguous index frames of H x W x 3 uint8 (channel
+ * fastest), as vcf_dct_dz_encode writes them with H = Hp, W = Wp.  The rows x
+ * cols grid cuts every frame into regions of (H / rows) x (W / cols) pixels,
+ * region r = i * cols + j at pixel (i * H / rows, j * W / cols): 1 x 1 is the
+ * whole plane, B x B the subbands of the DCT's subband layout.  counts_dev
+ * receives n_frames x rows * cols x 3 x 256 uint32 counters,
+ *     counts[((f * rows * cols + r) * 3 + c) * 256 + v]
+ *         = the samples of channel c in region r of frame f that equal v.
+ * Integer adds: the counts depend on no launch geometry and on no order.  The
+ * call zeroes the counters it writes itself (on `stream`, before the kernel).
+ * idx_dev needs no alignment (16-byte loads from the first 16-byte boundary of
+ * every row segment, bytes around them); counts_dev is 4-byte aligned.
+ * counts_capacity is the number of uint32 counters at counts_dev: only the
+ * first n_frames * rows * cols * 768 are written, and a smaller capacity is
+ * VCF_ERR_INVALID.  So are a null or misaligned pointer, a negative size, rows
+ * or cols < 1 and a grid that does not divide the frame (H % rows, W % cols);
+ * rows or cols > 16 and frames of more than 2^31 - 1 bytes are
+ * VCF_ERR_UNSUPPORTED; all before any device work, nothing written.
+ * n_frames = 0: VCF_OK, nothing enqueued.  H * W = 0: the counters are zeroed.
+ * Batches of more than 65535 frames run in launches of 65535. */
+int vcf_index_hist_u8(const uint8_t *idx_dev, int64_t n_frames, int32_t H, int32_t W, int32_t rows, int32_t cols,
+                      uint32_t *counts_dev, int64_t counts_capacity, void *stream);
+
 /* ---- cross-rank exchange on RCCL over xGMI -------------------
  * Frames shard across one process per GPU with no collective on the data
  * path; the one exchange step of the III / IPP drivers is after coding: an

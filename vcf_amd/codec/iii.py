@@ -91,6 +91,13 @@ class CoDec:
         self.encoding = args.subparser_name == "encode"
         # a multi-rank Group selects this rank's GPU (local rank) before any codec work
         self.group = group if group is not None else shard.Group()
+        # --target_bpp / --target_bytes / --q_from_files (not in the reference): 2D-DCT only
+        self.rate_control = any(v is not None for v in (getattr(args, "target_bpp", None),
+                                                        getattr(args, "target_bytes", None)))
+        self.q_from_files = bool(getattr(args, "q_from_files", False))
+        if self.rate_control or self.q_from_files:
+            from . import ratecontrol
+            ratecontrol.refuse_unless_dct(args, getattr(args, "transform", "2D-DCT"))
         self.transform_codec = codec if codec is not None else transform_codec(args)
         self.batch = batch
         self.encode_prefix = encode_prefix
@@ -113,7 +120,11 @@ class CoDec:
         n = len(inputs)
         lo, hi = shard.frame_range(n, g.rank, g.world)
         pairs = [(inputs[i], f"{self.encode_prefix}_%04d" % i) for i in range(lo, hi)]
-        local = self.transform_codec.encode_fns(pairs, batch=self.batch) if pairs else []
+        if self.rate_control and pairs:
+            from . import ratecontrol      # every frame at its own chosen -q, written to encoded_%04d_q.txt
+            local = ratecontrol.encode_files(self.transform_codec, pairs, self.args, batch=self.batch)
+        else:
+            local = self.transform_codec.encode_fns(pairs, batch=self.batch) if pairs else []
         self.sizes = g.all_gather_sizes(n, local)
         self.N_frames = n
         self.total_output_size = int(self.sizes.sum())
@@ -126,7 +137,11 @@ class CoDec:
         lo, hi = shard.frame_range(n, g.rank, g.world)
         pairs = [(f"{self.encode_prefix}_%04d" % i, f"{self.decode_prefix}_%04d.png" % i)
                  for i in range(lo, hi)]
-        local = self.transform_codec.decode_fns(pairs, batch=self.batch) if pairs else []
+        if self.q_from_files and pairs:
+            from . import ratecontrol
+            local = ratecontrol.decode_files(self.transform_codec, pairs, batch=self.batch)
+        else:
+            local = self.transform_codec.decode_fns(pairs, batch=self.batch) if pairs else []
         self.sizes = g.all_gather_sizes(n, local)
         self.total_output_size = int(self.sizes.sum())
         return self.total_output_size

@@ -314,11 +314,43 @@ def dwt_parser(description: str = "Exploiting spatial redundancy with the 2D dya
     return p
 
 
+def add_rate_control(enc, dec):
+    """Not in the reference: a byte budget per frame instead of -q (codec/ratecontrol.py).  Every
+    default leaves the -q path as it is."""
+    enc.add_argument("--target_bpp", type=float, default=None,
+                     help="Choose -q per frame so that its files take at most this many bits per pixel")
+    enc.add_argument("--target_bytes", type=int, default=None,
+                     help="Choose -q per frame so that its files take at most this many bytes")
+    enc.add_argument("--rate", choices=("estimate", "coded"), default="estimate",
+                     help="What the search probes: the histogram estimate or the real code-stream sizes")
+    enc.add_argument("--q_min", type=int, default=1, help="Smallest -q the search may choose")
+    enc.add_argument("--q_max", type=int, default=2048, help="Largest -q the search may choose")
+    dec.add_argument("--q_from_files", action="store_true", default=False,
+                     help="Read every frame's -q from the _q.txt file the rate control wrote beside it")
+
+
+def rate_control_parser(description: str = "2D-DCT coding under a byte budget: -q is chosen per image.",
+                        entropy: str = DEFAULT_EIC):
+    """`python rate-control.py ...`: 2D-DCT.py's options (deadzone) plus the budget."""
+    p, enc, dec = base_parser(description)
+    add_dct(enc, dec)
+    add_ycocg(enc, dec)
+    add_deadzone(enc, dec)
+    add_filter(enc, dec, entropy)
+    add_eic(enc, dec)
+    add_rate_control(enc, dec)
+    return p
+
+
 def iii_parser(description: str = "III coding: runs a 2D image codec for each image of a sequence.",
-               transform: str = "2D-DCT", entropy: str = DEFAULT_EIC):
-    """`python III.py ...` (III.py + the chain of the 2D codec it imports)."""
+               transform: str = "2D-DCT", entropy: str = DEFAULT_EIC, rate_control: bool = False):
+    """`python III.py ...` (III.py + the chain of the 2D codec it imports).  rate_control adds
+    --target_bpp, --target_bytes and --q_from_files, as III.py does; without it the Namespace is
+    the reference's."""
     p, enc, dec = base_parser(description)
     add_iii(enc, dec)
+    if rate_control:
+        add_rate_control(enc, dec)
     if transform == "2D-DWT":
         add_dwt(enc, dec)
     elif transform == "2D-MDCT":
