@@ -5,8 +5,8 @@ l=5, bior4.4, Q=32):
   python scripts/dwt_sched_ab.py FIELD encode|decode [--lifting] [-n N] [-r R] VALUE...
 
 e.g. `dec21_brows decode 60 90 108`, `enc_bands encode 1 2 4 8`, `band21 decode 0`,
-`lift_fused encode --lifting 0`.  Every setting runs the A/B library's build of
-the product code (vcf_dwt_dz_*_sched; "default" = a NULL schedule), interleaved
+`lift_fused encode --lifting 0`.  Every setting runs the A/B library's twins of
+the product entries (vcf_dwt_dz_*_sched; "default" = a NULL schedule), interleaved
 over R rounds of N launches in alternating order, timed with HIP events on the
 launch stream.  Prints one JSON line: median ms per launch and an output
 checksum per setting (a schedule never changes a byte)."""

@@ -219,6 +219,7 @@ from vcf_amd import _lib as L
 from vcf_amd.codec.tiff import strip_layout
 from vcf_amd.device import DeviceBuffer
 from vcf_amd.zlib_gpu import StripDeflater
+L.call("vcf_zlib_set_workspace_budget", int(sys.argv[2]))
 n, H, W = 24, 1080, 1920
 bases = [bench.synth_frame(H, W, seed=100 + s) for s in range(4)]
 k = np.concatenate([dct.encode(np.stack([bench.c4_frame(bases, i) for i in range(f, f + 8)]), Q=32)
@@ -238,15 +239,14 @@ assert per < total and not bad, bad[:20]
 
 def test_many_rounds_every_strip_equals_zlib():
     """Deterministic multi-round run: the workspace budget forced down to ~50 MB
-    (VCF_ZX_BUDGET, read once per process, so a child process) cuts 2 376 C4
+    (vcf_zlib_set_workspace_budget, per-process state, so a child process) cuts 2 376 C4
     strips into rounds of 43 that reuse one workspace; every strip against
     zlib.compress (a strip coded from the previous round's tables shows here)."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, VCF_ZX_BUDGET="50000000")
-    p = subprocess.run([sys.executable, "-c", _MULTI_ROUND, root], env=env, capture_output=True, text=True,
+    p = subprocess.run([sys.executable, "-c", _MULTI_ROUND, root, "50000000"], capture_output=True, text=True,
                        timeout=280)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert "bad 0" in p.stdout
@@ -389,7 +389,9 @@ import numpy as np
 sys.path[:0] = [sys.argv[1], sys.argv[2]]
 from deflate_cases import STRIP, corpus_by_length, describe_mismatch, lazy_rule, small_strip_frame
 from vcf_amd.device import DeviceBuffer
+from vcf_amd import _lib as L
 from vcf_amd.zlib_gpu import StripDeflater, workspace
+L.call("vcf_zlib_set_workspace_budget", int(sys.argv[3]))
 calls = [("corpus", [b for _, b in corpus_by_length()[STRIP]], STRIP),
          ("5000", [small_strip_frame(5000, 300, 60)], 5000)]
 dfl = StripDeflater()
@@ -413,7 +415,7 @@ print("all rounds ok")
 @pytest.mark.parametrize("per_round", [6, 1])
 def test_rounds_with_both_kinds(per_round):
     """The 64 KiB corpus call and the 5 000-byte call in rounds of 6 strips and of
-    one strip (VCF_ZX_BUDGET, read once per process: a child process): K1's list
+    one strip (vcf_zlib_set_workspace_budget, per-process state: a child process): K1's list
     is reset every round and the side kernels read the list of this round's slots."""
     import os
     import subprocess
@@ -421,8 +423,7 @@ def test_rounds_with_both_kinds(per_round):
     from vcf_amd.zlib_gpu import workspace
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     budget = per_round * workspace(1) + (4096 if per_round > 1 else 0)
-    env = dict(os.environ, VCF_ZX_BUDGET=str(budget))
-    p = subprocess.run([sys.executable, "-c", _ROUNDS, root, os.path.join(root, "tests")], env=env,
+    p = subprocess.run([sys.executable, "-c", _ROUNDS, root, os.path.join(root, "tests"), str(budget)],
                        capture_output=True, text=True, timeout=120)
     print(p.stdout[-3000:])
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]

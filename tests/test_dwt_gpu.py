@@ -406,3 +406,44 @@ def test_dwt_schedule_unknown_field():
         DW.decode(sb, 16, 16, "db5", 2, 32, schedule={"bands": 1, "band21": 0})
     with pytest.raises(ValueError):
         DW.encode(frame, "db5", 2, 32, variant=1, schedule={"enc_bands": 2})
+
+
+def test_dwt_sched_twins_reach_the_product_object():
+    """With the A/B library loaded next to the product library -- both hold csrc/vcf_dwt.hip's object, so
+    both define vcf_dwt_dz_encode / _decode -- the product entry, its _sched twin with NULL and the twin
+    under a forced schedule give the same bytes on a 37 x 45 frame (odd planes at both levels)."""
+    import ctypes
+    import vcf_amd._lib as L
+    import vcf_amd.dwt as DW
+    from vcf_amd.device import DeviceBuffer
+    L.ab()
+    H, W, levels, Q = 37, 45, 2, 32
+    wavelet = DW.wavelet_index("db5")
+    shapes, pb, wb = DW.layout(H, W, levels)
+    out_bytes = 4 * shapes[0][0] * shapes[0][1] * 3
+    forced = L.DwtSchedule(enc_pipe=0, band21=0)
+
+    def run(name, src, nbytes, sched):
+        din, dws = DeviceBuffer.from_array(src), DeviceBuffer(wb)
+        dout = DeviceBuffer.from_array(np.full(nbytes, 0xA5, np.uint8))   # (a call that wrote nothing would show)
+        try:
+            args = (din.ptr, 1, H, W, wavelet, levels, Q, dout.ptr, dws.ptr, None)
+            if sched == "product":
+                L.call(name, *args)
+            else:
+                L.call_ab(name + "_sched", None if sched is None else ctypes.byref(sched), *args)
+            return dout.download(np.empty(nbytes, np.uint8))
+        finally:
+            din.free()
+            dout.free()
+            dws.free()
+
+    frame = _noise(1, H, W, 3745)[0]
+    packed = run("vcf_dwt_dz_encode", frame, pb, "product")
+    assert not np.all(packed == 0xA5)
+    assert np.array_equal(run("vcf_dwt_dz_encode", frame, pb, None), packed)
+    assert np.array_equal(run("vcf_dwt_dz_encode", frame, pb, forced), packed)
+    rgb = run("vcf_dwt_dz_decode", packed, out_bytes, "product")
+    assert not np.all(rgb == 0xA5)
+    assert np.array_equal(run("vcf_dwt_dz_decode", packed, out_bytes, None), rgb)
+    assert np.array_equal(run("vcf_dwt_dz_decode", packed, out_bytes, forced), rgb)

@@ -15,8 +15,10 @@ from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "vcf_amd", "csrc")
 # the product library's environment reads, all of them
-GETENV_ALLOWED = {("vcf_deflate.hip", "VCF_ZX_BUDGET"), ("vcf_png.cpp", "VCF_PNG_NO_LIBDEFLATE"),
-                  ("vcf_comm.cpp", "VCF_COMM_TIMEOUT_MS")}
+GETENV_ALLOWED = {("vcf_png.cpp", "VCF_PNG_NO_LIBDEFLATE"), ("vcf_comm.cpp", "VCF_COMM_TIMEOUT_MS")}
+# the product sources' compile-time switches, all of them: two instruments of the deflate, the
+# inflate's window-check build (csrc/ab/vcf_inflate_wincheck.hip), the DWT kernels alone (scripts/micro/)
+SWITCHES_ALLOWED = {"VCF_ZLIB_PROF", "VCF_ZX_WINCHECK", "VCF_INFLATE_WINCHECK_BUILD", "VCF_DWT_KERNELS_ONLY"}
 
 
 def test_product_sources_read_no_other_environment():
@@ -27,6 +29,37 @@ def test_product_sources_read_no_other_environment():
             for m in re.finditer(r"getenv\(\s*(\"(\w+)\")?", src):
                 found.append((os.path.basename(path), m.group(2)))
     assert sorted(found) == sorted(GETENV_ALLOWED), found
+
+
+def test_product_sources_have_no_other_compile_time_switch():
+    """A measured and decided A/B leaves one form in the product sources, not a macro with both:
+    every VCF_ name a preprocessor conditional tests (an `#ifndef VCF_X` / `#define VCF_X <default>`
+    pair among them), include guards aside, is on the list."""
+    found = set()
+    paths = [p for ext in ("hip", "h", "cpp") for p in glob.glob(os.path.join(CSRC, "*." + ext))]
+    for path in sorted(paths + glob.glob(os.path.join(ROOT, "include", "*.h"))):
+        src = re.sub(r"/\*.*?\*/", "", open(path, errors="replace").read(), flags=re.S)
+        src = re.sub(r"//[^\n]*", "", src)
+        guards = set(re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[ \t]*\n[ \t]*#[ \t]*define[ \t]+\1[ \t]*$", src, flags=re.M))
+        for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", src, flags=re.M):
+            found |= set(re.findall(r"\bVCF_\w+", line)) - guards
+    assert found == SWITCHES_ALLOWED, sorted(found ^ SWITCHES_ALLOWED)
+
+
+def test_removed_switches_are_gone():
+    """The decided switches' names, anywhere a build could still set them: the DWT's second build,
+    the two small A/B macros, and every VCF_ZX_ macro of the deflate but its window check."""
+    hits = []
+    for sub in (os.path.join("vcf_amd", "csrc"), "include", "scripts"):
+        for dirpath, _, names in os.walk(os.path.join(ROOT, sub)):
+            for name in sorted(names):
+                path = os.path.join(dirpath, name)
+                src = open(path, errors="replace").read()
+                pat = r"VCF_DWT_SCHED_BUILD|VCF_B21_SPLIT|VCF_SDWA_ASM"
+                if sub.endswith("csrc"):
+                    pat += r"|VCF_ZX_(?!WINCHECK\b)\w+"
+                hits += [(os.path.relpath(path, ROOT), m) for m in re.findall(pat, src)]
+    assert not hits, hits
 
 
 def test_public_header_has_no_kernel_setter():

@@ -20,8 +20,9 @@ AB_LIB = os.path.join(PKG, "libvcf_amd_ab.so")
 # the A/B archive's own sources, linked with these product objects
 AB_SOURCES = ["ab/vcf_dct_dz_ab.hip", "ab/vcf_dwt_ab.hip", "ab/vcf_dwt_sched.hip", "ab/vcf_inflate_wincheck.hip",
               "ab/vcf_kernel_choice.hip"]
-# (vcf_cbaac_gpu, vcf_cbaac for its bound, and vcf_ipp: the entries ab/vcf_kernel_choice.hip calls)
-AB_LINK = ["vcf_runtime.hip", "vcf_dct_any.hip", "vcf_cbaac_gpu.hip", "vcf_cbaac.cpp", "vcf_ipp.hip"]
+# (vcf_cbaac_gpu, vcf_cbaac for its bound, and vcf_ipp: the entries ab/vcf_kernel_choice.hip calls;
+# vcf_dwt: the entries ab/vcf_dwt_sched.hip calls)
+AB_LINK = ["vcf_runtime.hip", "vcf_dct_any.hip", "vcf_cbaac_gpu.hip", "vcf_cbaac.cpp", "vcf_ipp.hip", "vcf_dwt.hip"]
 SOURCES = ["vcf_runtime.hip", "vcf_dct_dz.hip", "vcf_dct_any.hip", "vcf_quant.hip", "vcf_dwt.hip", "vcf_cbaac.cpp",
            "vcf_cbahc.cpp", "vcf_ipp.hip", "vcf_ipp_rdo.hip",
            "vcf_png.cpp", "vcf_comm.cpp", "vcf_cbaac_gpu.hip", "vcf_plugins.hip", "vcf_deflate.hip",

@@ -1782,39 +1782,6 @@ using namespace vcf;
 
 extern "C" {
 
-int vcf_wavelet_index(const char *name, int32_t *index)
-{
-    if (!name || !index) return set_error(VCF_ERR_INVALID, "null pointer");
-    for (int i = 0; i < kNumWavelets; ++i)
-        if (strcmp(kWavelets[i].name, name) == 0) {
-            *index = i;
-            return VCF_OK;
-        }
-    return set_error(VCF_ERR_INVALID, "unknown wavelet '%s'", name);
-}
-
-int vcf_dwt_layout(int32_t H, int32_t W, int32_t levels, int32_t *sub_h, int32_t *sub_w, int64_t *packed_bytes,
-                   int64_t *workspace_bytes_per_frame)
-{
-    if (H <= 0 || W <= 0 || levels < 1 || levels > kMaxLevels) return set_error(VCF_ERR_INVALID, "bad layout args");
-    DwtGeom g;
-    dwt_geom(H, W, levels, 2, g);
-    for (int l = 1; l <= levels; ++l) {
-        if (sub_h) sub_h[l - 1] = g.hs[l];
-        if (sub_w) sub_w[l - 1] = g.ws[l];
-    }
-    if (packed_bytes) *packed_bytes = g.packed_bytes;
-    if (workspace_bytes_per_frame) *workspace_bytes_per_frame = 3 * plane_doubles(g) * (int64_t)sizeof(double);
-    return VCF_OK;
-}
-
-int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
-                      int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
-{
-    return vcf_dwt_dz_encode_variant(0, rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev,
-                                     stream);
-}
-
 // one stream's level chain of the encode (variants 0-12; the pipelined forms
 // call it per chunk of frames with their hook)
 static int encode_chain(int variant, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
@@ -1964,13 +1931,6 @@ int vcf_dwt_dz_encode_variant(int variant, const uint8_t *rgb_dev, int64_t n_fra
     }
     return encode_chain(variant, rgb_dev, n_frames, H, W, wavelet, levels, Q, packed_dev, workspace_dev, s, nullptr,
                         sep_area, no_band);
-}
-
-int vcf_dwt_dz_decode(const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
-                      int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
-{
-    return vcf_dwt_dz_decode_variant(0, packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev,
-                                     stream);
 }
 
 // one stream's level chain of the decode (variants 0-5)

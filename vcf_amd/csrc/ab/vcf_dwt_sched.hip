@@ -1,14 +1,12 @@
-// vcf_dwt_sched.hip -- the product 2D-DWT (csrc/vcf_dwt.hip: the same kernels
-// and launch code) built for the A/B library with the kernel schedule as an
-// argument: vcf_dwt_dz_*_sched take a vcf_dwt_schedule (include/vcf_amd_ab.h)
-// in front of the product signature.  Under VCF_DWT_SCHED_BUILD vcf_dwt.hip
-// leaves out its extern "C" names (ab/vcf_dwt_ab.hip defines vcf_dwt_dz_encode,
-// _decode, vcf_dwt_layout and vcf_wavelet_index in this library).  Every
-// schedule gives the product's bytes (tests/test_dwt_gpu.py); the A/B runs are
-// scripts/dwt_sched_ab.py.
-#define VCF_DWT_SCHED_BUILD 1
+// vcf_dwt_sched.hip -- the product 2D-DWT entries with a vcf_dwt_schedule
+// (include/vcf_amd_ab.h) in front of the product signature.  No kernel is built
+// here: the twins call the product's own entries (vcf_internal.h; csrc/vcf_dwt.hip
+// is linked into this library).  Every schedule gives the product's bytes
+// (tests/test_dwt_gpu.py); the A/B runs are scripts/dwt_sched_ab.py.
 #include "vcf_amd_ab.h"
-#include "vcf_dwt.hip"
+#include "vcf_internal.h"
+
+using namespace vcf;
 
 // NULL = the library's rules
 static DwtSchedule schedule_of(const vcf_dwt_schedule *p)

@@ -95,8 +95,7 @@ inline int current_device()
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
     return dev;
 }
-// the budget in effect on the current device (VCF_ZX_BUDGET bytes overrides the
-// default: A/B of the round size); thread-safe, computed once per device
+// the budget in effect on the current device; thread-safe, the default computed once per device
 inline int64_t ws_budget()
 {
     const int dev = current_device();
@@ -109,8 +108,7 @@ inline int64_t ws_budget()
         size_t free_b = 0, total = 0;
         if (hipMemGetInfo(&free_b, &total) == hipSuccess)
             v = std::min(kWsBudgetMax, std::max(kWsBudget, (int64_t)(free_b / 4)));
-        const char *e = getenv("VCF_ZX_BUDGET");
-        dflt[dev] = e && atoll(e) > 0 ? atoll(e) : v;
+        dflt[dev] = v;
     });
     return dflt[dev];
 }
@@ -126,10 +124,7 @@ struct ZRounds {
     }
 };
 constexpr int kK2bThreads = 1024;    // K2b: 16 waves per strip, one listed position per wave at a time
-#ifndef VCF_ZX_K2BSPLIT   // A/B (diagnostic builds): K2b workgroups per strip
-#define VCF_ZX_K2BSPLIT 4
-#endif
-constexpr int kK2bSplit = VCF_ZX_K2BSPLIT;   // K2b: workgroups per strip, the listed positions split between them
+constexpr int kK2bSplit = 4;         // K2b: workgroups per strip, the listed positions split between them
 // A strip is parsed LAZY (on demand, zlib's order of work) when K1 finds fewer than
 // one distinct hash per kLazyDiv positions among its 64-position groups: such
 // repetitive content leaves most positions inside long matches, which zlib -- and
@@ -139,24 +134,12 @@ constexpr int kK2bSplit = VCF_ZX_K2BSPLIT;   // K2b: workgroups per strip, the l
 // too: its side stream of K2a/K2b/K3 no longer competes with the lazy parse for
 // the CUs (C4 deflate 160 -> 107 ms), and raw RGB strips still take K2 (561 ms
 // either way; every strip lazy: 864 ms).
-#ifndef VCF_ZX_LAZYDIV   // A/B (diagnostic builds)
-#define VCF_ZX_LAZYDIV 2
-#endif
-constexpr uint32_t kLazyDiv = VCF_ZX_LAZYDIV;
+constexpr uint32_t kLazyDiv = 2;
 
 __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 
 #ifndef VCF_ZLIB_PROF
 #define VCF_ZLIB_PROF 0
-#endif
-#ifndef VCF_ZX_NOCAP   // A/B (diagnostic builds): lane compares run on to MAX_MATCH
-#define VCF_ZX_NOCAP 0
-#endif
-#ifndef VCF_ZX_NOPRIO   // A/B (diagnostic builds): the side stream at normal priority
-#define VCF_ZX_NOPRIO 0
-#endif
-#ifndef VCF_ZX_COHERENT   // A/B (diagnostic builds): agent-scope loads of the K1 / head tables in the lazy parse
-#define VCF_ZX_COHERENT 0
 #endif
 #ifndef VCF_ZX_WINCHECK   // (diagnostic) the lazy window checked against the strip at every call
 #define VCF_ZX_WINCHECK 0
@@ -165,23 +148,6 @@ __device__ __forceinline__ uint32_t lane_id() { return __lane_id(); }
 // first failure: [0] 1 + kind (1: window at p, 2: window at a candidate), [1] strip, [2] p,
 // [3] position, [4] window byte, [5] strip byte, [6] wbase, [7] count of failures
 __device__ unsigned int g_zdbg[8];
-#endif
-#ifndef VCF_ZX_LDSZERO
-#define VCF_ZX_LDSZERO 0
-#endif
-#ifndef VCF_ZX_EARLY0   // A/B (diagnostic builds): round 0's candidate reads before the head compare
-// (round 6: 0 -- the head compare no longer waits for the candidate list and the far
-// candidates' bytes, and round 0's far reads share one round trip with its scan_end
-// bytes: C4 deflate 102.3 -> 97.2 ms, ABBA, profiles/r06_zab_v2.json)
-#define VCF_ZX_EARLY0 0
-#endif
-#ifndef VCF_ZX_PREDICT   // A/B (diagnostic builds): prefetch the exactly predicted next call position
-// (round 6: 1 -- 70 % -> 93 % of the calls find their candidates prefetched; C4 deflate
-// 101.3 -> 95.3 ms, ABBA, profiles/r06_zab_v3.json; 2: also p + 1, 98.4 ms)
-#define VCF_ZX_PREDICT 1
-#endif
-#ifndef VCF_ZX_SERIAL   // A/B (diagnostic builds): every kernel of a round on the caller's stream
-#define VCF_ZX_SERIAL 0
 #endif
 #if VCF_ZLIB_PROF
 // diagnostic build only (scripts/zprof_build.sh): per-phase clock totals of the parse kernels
@@ -205,20 +171,14 @@ __device__ __forceinline__ uint32_t lane_val(uint32_t v, uint32_t l)
 {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)uni(l));
 }
-// The parse kernels' workgroups hold VCF_ZX_WG waves, one strip each, every wave with
-// its own LDS section and no data shared between them: a wave's LDS writes and reads
-// need only the ordering of its own instructions (the LDS serves one wave's DS
-// instructions in order) and the fence's wait counts -- no workgroup barrier, which
-// would tie the waves' independent control flows together.
-#ifndef VCF_ZX_WG   // A/B (diagnostic builds): strips (waves) per parse workgroup
-#define VCF_ZX_WG 1
-#endif
-constexpr int kParseWG = VCF_ZX_WG;
+// The parse kernels' workgroups hold one wave, one strip each (two waves per
+// workgroup, each with its own LDS section and wave-local synchronisation, changed
+// nothing: 96.6 ms for C4): the wave's LDS writes and reads are
+// ordered by the fence and the workgroup barrier.
 __device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    if (kParseWG == 1) __builtin_amdgcn_s_barrier();
-    else __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_barrier();
 }
 __device__ __forceinline__ uint32_t excl_scan(uint32_t v, uint32_t &total)
 {
@@ -353,14 +313,10 @@ __device__ __forceinline__ uint64_t digit_mask(uint32_t d, bool valid)
 // the same mask from one round per distinct digit (a lane's digit compared with a
 // leader's by readlane + ballot): fewer instructions when a group holds few digits, as
 // repetitive content does; past kDigitRounds rounds the bit-sliced form finishes
-#ifndef VCF_ZX_DIGITLOOP   // A/B (diagnostic builds)
-#define VCF_ZX_DIGITLOOP 1
-#endif
 constexpr int kDigitRounds = 6;
 template <int BITS>
 __device__ __forceinline__ uint64_t digit_mask_r(uint32_t d, bool valid)
 {
-    if (!VCF_ZX_DIGITLOOP) return digit_mask<BITS>(d, valid);
     uint64_t rem = __ballot(valid), m0 = 0;
     for (int r = 0; r < kDigitRounds && rem; ++r) {
         const uint32_t hl = lane_val(d, (uint32_t)__ffsll((unsigned long long)rem) - 1);
@@ -639,11 +595,7 @@ __global__ __launch_bounds__(64 * kSortWaves) void zlib_sort_kernel(const uint8_
         sums[1] = b;
         *reinterpret_cast<uint32_t *>(S.ws + kSumOff + 16) = 0;   // K2's worklist length
         *reinterpret_cast<uint32_t *>(S.ws + kSumOff + 24) = dsum;   // the lazy parse's dispatch order key
-#ifdef VCF_ZX_LAZYALL   // A/B (diagnostic builds): every strip through the lazy parse
-        const bool lazy = true;
-#else
         const bool lazy = dsum * kLazyDiv < np;
-#endif
         *reinterpret_cast<uint32_t *>(S.ws + kSumOff + 20) = lazy ? 1u : 0u;   // parse order
         if (!lazy) {   // onto the side kernels' list
             const uint32_t i = atomicAdd(reinterpret_cast<uint32_t *>(ws + kSumOff + 40), 1u);
@@ -976,32 +928,19 @@ static_assert(offsetof(ParseSmem, lfreq) % 16 == 0, "packed adds into lfreq; the
 // CU (C4 deflate, ms: 34 560 B 245, 18 432 B 212, 14 080 B 189, 9 984 B 182,
 // 8 448 B 176, 7 168 B 172, 5 120 B 165, 3 840 B 161; 3 072 / 2 304 B 161 / 159:
 // no more than 16 workgroups reside on a CU).  Round 6 lays the window over the
-// flush-only part of ParseSmem (VCF_ZX_ALIAS): 9 216 bytes at the same 16 strips per CU.
-#ifndef VCF_ZX_ALIAS   // A/B (diagnostic builds): the lazy window laid over the flush-only LDS
-// (round 6: 1 -- the window grows from 3 840 to 9 216 bytes at the same 16 strips per CU,
-// so chain candidates up to 7 872 bytes back read LDS instead of HBM)
-#define VCF_ZX_ALIAS 1
-#endif
-#ifndef VCF_ZX_LAZYWIN   // A/B (diagnostic builds): the window's bytes (a multiple of 256)
-#define VCF_ZX_LAZYWIN (VCF_ZX_ALIAS ? 9216 : 3840)
-#endif
-constexpr uint32_t kLazyWin = VCF_ZX_LAZYWIN;
-#ifndef VCF_ZX_LWIN   // A/B (diagnostic builds): positions per lazy hd[] / idx[] register window (512 or 256)
-// (round 6: 256 -- uint2 windows, two readlanes per lookup instead of four, 8 fewer VGPRs:
-// C4 deflate 95.5 -> 89.5 ms, ABBA, profiles/r06_zab_v5.json)
-#define VCF_ZX_LWIN 256
-#endif
-constexpr uint32_t kLWin = VCF_ZX_LWIN;
-static_assert(kLWin == 512 || kLWin == 256, "lazy windows of 512 or 256 positions");
-using LVec = std::conditional_t<kLWin == 512, uint4, uint2>;
+// flush-only part of ParseSmem: the window grows from 3 840 to 9 216 bytes at the same 16
+// strips per CU, so chain candidates up to 7 872 bytes back read LDS instead of HBM.
+constexpr uint32_t kLazyWin = 9216;   // the window's bytes (a multiple of 256)
+// positions per lazy hd[] / idx[] register window, 4 per lane in a uint2 (round 6: 256, not
+// 512 in uint4s -- two readlanes per lookup instead of four, 8 fewer VGPRs: C4 deflate
+// 95.5 -> 89.5 ms, ABBA, profiles/r06_zab_v5.json)
+constexpr uint32_t kLWin = 256;
+using LVec = uint2;
 constexpr uint32_t kLazyAhead = 320;
 // the near distance the window keeps behind p after a shift: candidates at most
 // this far back read the window, farther ones (zlib reaches MAX_DIST back) read
 // the strip in HBM (Wave::far_*); shifts come every ~1 KB
-#ifndef VCF_ZX_SLACK   // A/B (diagnostic builds): bytes a window shift leaves ahead
-#define VCF_ZX_SLACK (kLazyWin >= 8192 ? 1024 : 512)
-#endif
-constexpr uint32_t kShiftSlack = VCF_ZX_SLACK;   // bytes a shift leaves ahead
+constexpr uint32_t kShiftSlack = 1024;   // bytes a shift leaves ahead
 constexpr uint32_t kNearDist = kLazyWin >= MAX_DIST + kLazyAhead + kShiftSlack ? (uint32_t)MAX_DIST
                                                                                : kLazyWin - kLazyAhead - kShiftSlack;
 static_assert(kLazyWin % 256 == 0 && kNearDist >= 512, "window too short");
@@ -1022,7 +961,7 @@ struct Wave {
     uint32_t *out32;
     uint32_t out_words;           // slot capacity in words
     uint32_t good;                // cfg.good: the reduced-chain results from prev_length >= good
-    uint32_t lazy = 0;            // cfg.lazy (VCF_ZX_PREDICT)
+    uint32_t lazy = 0;            // cfg.lazy (the prefetch's prediction)
     uint32_t bitpos = 0;          // bits written so far (uniform)
     uint32_t nsym = 0;            // symbols of the current block (uniform)
     // 512-position windows: lane l holds positions base + 8l .. base + 8l + 7
@@ -1031,17 +970,19 @@ struct Wave {
     uint32_t bv0, bv1;
     bool overflow = false;
     BlockTrees T;
-    // LAZY: the sliding window in LDS, the bucket order, and a 512-position window of idx[]
+    // LAZY: the sliding window in LDS, the bucket order, and the windows of idx[] (liv below)
     uint8_t *lwin = nullptr;      // window byte i is input position wbase + i
     uint32_t wbase = 0;
     bool wslid = false;           // zlib's window has slid: the bytes past n are the stale copy WSIZE back
     const uint16_t *idx = nullptr, *sorted = nullptr;
     uint32_t ibase = 0x80000000u;
-    uint4 iv;
-    // the chain candidates of the positions the next call will most likely be at (p + 1,
-    // and p + the match length), requested at the end of a call: their global latency
-    // overlaps the parse step in between (~70 % of the calls are at one of the two)
-    uint32_t pfa_p = 0xffffffffu, pfa0 = 0, pfa1 = 0, pfb_p = 0xffffffffu, pfb0 = 0, pfb1 = 0;
+    // the chain candidates of the position the next call will be at (predict_next), requested
+    // at the end of a call: their global latency overlaps the parse step in between
+    uint32_t pfa_p = 0xffffffffu, pfa0 = 0, pfa1 = 0;
+    // What is left of the retired second slot: its position, always "empty".  longest_match
+    // still compares p with it (never equal: p < n), because without the member and the two
+    // compares the compiler emits other code for the parse than the code that was measured.
+    uint32_t pf_none = 0xffffffffu;
 #if VCF_ZX_WINCHECK
     uint32_t dbg_strip = 0;
     __device__ __forceinline__ void wincheck(uint32_t kind, uint32_t P, bool bad, uint32_t got, uint32_t want)
@@ -1075,47 +1016,15 @@ struct Wave {
     }
 
     // ---- the windows ---------------------------------------------------
-    // LAZY: 512-aligned windows of hd[] and idx[], each with the next window requested
-    // as soon as the current one is in use (the parse only moves forward, at most
-    // MAX_MATCH positions at a time, so it always enters the next window)
-    uint4 hv_n, iv_n;
-    // VCF_ZX_COHERENT (A/B): the workspace tables K1 wrote, read at agent scope
-    __device__ __forceinline__ static uint4 wload4(const uint16_t *a)
-    {
-#if VCF_ZX_COHERENT
-        const uint32_t *v = reinterpret_cast<const uint32_t *>(a);
-        return make_uint4(ld_l2(v), ld_l2(v + 1), ld_l2(v + 2), ld_l2(v + 3));
-#else
-        return *reinterpret_cast<const uint4 *>(a);
-#endif
-    }
-    __device__ __forceinline__ static uint32_t wload16(const uint16_t *a)
-    {
-#if VCF_ZX_COHERENT
-        return ld_l2(a);
-#else
-        return *a;
-#endif
-    }
-    // VCF_ZX_LWIN = 256 (A/B): the lazy windows of hd[] / idx[] as 256 positions, 4 per lane in
-    // a uint2 (8 fewer VGPRs than 512 in uint4s: room for more waves per SIMD)
+    // LAZY: kLWin-aligned windows of hd[] and idx[] (4 positions per lane in a uint2), each
+    // with the next window requested as soon as the current one is in use (the parse only
+    // moves forward, at most MAX_MATCH positions at a time, so it always enters the next window)
     LVec lhv, liv, lhv_n, liv_n;
-    __device__ __forceinline__ static LVec wloadL(const uint16_t *a)
-    {
-#if VCF_ZX_LWIN == 512
-        return wload4(a);
-#else
-        return *reinterpret_cast<const uint2 *>(a);
-#endif
-    }
+    __device__ __forceinline__ static LVec wloadL(const uint16_t *a) { return *reinterpret_cast<const uint2 *>(a); }
     __device__ __forceinline__ static uint32_t pickL(const LVec &v, uint32_t l, uint32_t d)   // dword d of lane l
     {
-#if VCF_ZX_LWIN == 512
-        return pick4(v, l, d);
-#else
         const uint32_t a = lane_val(v.x, l), b = lane_val(v.y, l);
         return d == 0 ? a : b;
-#endif
     }
     __device__ __forceinline__ void lazy_windows(uint32_t p)
     {
@@ -1437,8 +1346,8 @@ struct Wave {
     {
         const uint16_t *vs = sorted;
         const uint32_t g0 = lane_id(), g1 = 64 + lane_id();
-        c0 = wload16(vs + (g0 < ip ? ip - 1 - g0 : 0u));
-        c1 = wload16(vs + (g1 < ip ? ip - 1 - g1 : 0u));
+        c0 = vs[g0 < ip ? ip - 1 - g0 : 0u];
+        c1 = vs[g1 < ip ? ip - 1 - g1 : 0u];
     }
     __device__ __forceinline__ uint32_t idx_known(uint32_t q)   // idx[q] from the windows, or ~0 if outside them
     {
@@ -1448,13 +1357,15 @@ struct Wave {
         const uint32_t o = off & (kLWin - 1), e = o % per;
         return (pickL(off < kLWin ? liv : liv_n, o / per, e >> 1) >> ((e & 1) * 16)) & 0xffffu;
     }
-    // VCF_ZX_PREDICT (A/B): the position deflate_slow calls longest_match at next follows
+    // The position deflate_slow calls longest_match at next follows
     // from this call's result and prev_length: with match_length ml (this call's length,
     // clamped to the lookahead, TOO_FAR applied; prev_length when nothing was found), the
     // previous match is emitted when prev_length >= MIN_MATCH and ml <= prev_length (next
     // call at p - 1 + prev_length), else a match of at least `lazy` is emitted at the next
-    // step (next call at p + ml), else the parse moves to p + 1.  Slot a takes that
-    // position; slot b (PREDICT 2) p + 1 as well, for the calls the hash head skips.
+    // step (next call at p + ml), else the parse moves to p + 1.  The one prefetch slot
+    // takes that position (round 6: 70 % -> 93 % of the calls find their candidates
+    // prefetched against guessing p + 1 and p + the match length; C4 deflate 101.3 -> 95.3 ms,
+    // ABBA, profiles/r06_zab_v3.json; a second slot for p + 1 as well: 98.4 ms).
     __device__ __forceinline__ uint32_t predict_next(uint32_t p, bool found, uint32_t len, uint32_t pos,
                                                      uint32_t prev_len) const
     {
@@ -1468,20 +1379,10 @@ struct Wave {
     __device__ __forceinline__ void prefetch_next(uint32_t p, uint32_t len, bool found = false, uint32_t pos = 0,
                                                   uint32_t prev_len = 0)
     {
-#if VCF_ZX_PREDICT
         const uint32_t qa = predict_next(p, found, len, pos, prev_len);
-        const uint32_t qb = VCF_ZX_PREDICT == 2 ? p + 1 : qa;
-#else
-        const uint32_t qa = p + 1, qb = p + (len >= (uint32_t)MIN_MATCH ? len : 1u);
-#endif
         const uint32_t ia = idx_known(qa);
         pfa_p = ia != 0xffffffffu && qa + MIN_MATCH <= n ? qa : 0xffffffffu;
         if (pfa_p != 0xffffffffu) fetch_cands(ia, pfa0, pfa1);
-        if constexpr (VCF_ZX_PREDICT != 1) {   // (1: one exact slot; b unused)
-            const uint32_t ib = qb != qa ? idx_known(qb) : 0xffffffffu;
-            pfb_p = ib != 0xffffffffu && qb + MIN_MATCH <= n ? qb : 0xffffffffu;
-            if (pfb_p != 0xffffffffu) fetch_cands(ib, pfb0, pfb1);
-        }
     }
     __device__ __forceinline__ bool longest_impl(uint32_t p, uint32_t hdp, uint32_t prev_len, uint32_t chain,
                                                  uint32_t nice, uint32_t limit, uint32_t &len, uint32_t &pos)
@@ -1506,7 +1407,7 @@ struct Wave {
     {
 #if VCF_ZLIB_PROF
         const unsigned long long th0 = clock64();
-        if (p == pfa_p || p == pfb_p) ++n_pf;
+        if (p == pfa_p || p == pf_none) ++n_pf;
 #endif
         {
             // the first candidate (chain order) reaching max(nice, prev_len+1), else the
@@ -1533,9 +1434,8 @@ struct Wave {
             if (p == pfa_p) {
                 pre0 = pfa0;
                 pre1 = pfa1;
-            } else if (p == pfb_p) {
-                pre0 = pfb0;
-                pre1 = pfb1;
+            } else if (p == pf_none) {   // (never: see pf_none)
+                pre0 = pre1 = 0;
             } else {
                 fetch_cands(ip, pre0, pre1);
             }
@@ -1550,7 +1450,7 @@ struct Wave {
                 RoundRd r;
                 const uint32_t gk = b + lane_id();
                 r.v = gk < chain && gk < ip;
-                r.c = !r.v ? 0u : b == 0 ? pre0 : b == 64 ? pre1 : wload16(sorted + ip - 1 - gk);
+                r.c = !r.v ? 0u : b == 0 ? pre0 : b == 64 ? pre1 : *(sorted + ip - 1 - gk);
                 // sorted[] runs on past the bucket: a candidate of another bucket can be any
                 // position, so the bucket end must not be judged from bytes read at it before
                 // it is known to be p's: p's own bucket holds only earlier positions, and those
@@ -1572,9 +1472,10 @@ struct Wave {
                 }
                 return r;
             };
-            // round 0's reads in the round (VCF_ZX_EARLY0 = 1: issued with the head compare's)
-            RoundRd r0;
-            if (VCF_ZX_EARLY0) r0 = rd(0);
+            // (round 0's reads are issued inside the round, not here with the head compare's:
+            // the head compare then does not wait for the candidate list and the far candidates'
+            // bytes, and round 0's far reads share one round trip with its scan_end bytes -- C4
+            // deflate 102.3 -> 97.2 ms, ABBA, profiles/r06_zab_v2.json)
             const uint32_t hp = hash_at(wp);
             const uint32_t l1 = wave_lcp_at(hdp, wp);
 #if VCF_ZLIB_PROF
@@ -1605,7 +1506,7 @@ struct Wave {
                 const unsigned long long tr0 = clock64();
 #endif
                 const uint32_t gk = b + lane_id();
-                const RoundRd rr = VCF_ZX_EARLY0 && b == 0 ? r0 : rd(b);
+                const RoundRd rr = rd(b);
                 bool v = rr.v;
                 const bool far = rr.far;
                 const uint32_t c = rr.c, wc = rr.wc, c4 = rr.c4;
@@ -1652,9 +1553,9 @@ struct Wave {
                         const uint32_t q = x16[0] ? 0u : x16[1] ? 4u : x16[2] ? 8u : 12u;
                         l = q + ((uint32_t)__builtin_ctz(x16[0] ? x16[0] : x16[1] ? x16[1] : x16[2] ? x16[2] : x16[3]) >> 3);
                     } else if (!far) {
-                        l = lane_lcp(wc, wp, VCF_ZX_NOCAP ? (uint32_t)MAX_MATCH : Tn, 16u);
+                        l = lane_lcp(wc, wp, Tn, 16u);
                     } else {
-                        l = far_lcp(c, wp, VCF_ZX_NOCAP ? (uint32_t)MAX_MATCH : Tn, 16u);
+                        l = far_lcp(c, wp, Tn, 16u);
                     }
                 }
 #if VCF_ZLIB_PROF
@@ -1792,7 +1693,7 @@ struct Wave {
         nsym = 0;
         if (last) windup();
         if constexpr (LAZY) {
-            if (VCF_ZX_ALIAS && !last) reload();   // the flush used the window's LDS
+            if (!last) reload();   // the flush used the window's LDS
         }
     }
 };
@@ -1802,11 +1703,7 @@ struct ParseShared {
     ParseSmem sm;
 };
 template <>
-#ifndef VCF_ZX_LDSPAD   // (diagnostic) extra LDS per lazy-parse workgroup: fewer strips per CU
-#define VCF_ZX_LDSPAD 0
-#endif
 struct ParseShared<true> {
-#if VCF_ZX_ALIAS
     union {
         ParseSmem sm;
         struct {
@@ -1814,25 +1711,9 @@ struct ParseShared<true> {
             uint32_t win32[kLazyWin / 4];                    // the sliding window (Wave::ensure)
         } w;
     };
-#else
-    ParseSmem sm;
-    struct {
-        uint32_t win32[kLazyWin / 4];   // the sliding window of the strip (Wave::ensure)
-    } w;
-#endif
-#if VCF_ZX_LDSPAD
-    uint32_t pad[VCF_ZX_LDSPAD / 4];
-#endif
 };
-static_assert(VCF_ZX_LDSPAD || VCF_ZX_WG != 1 || sizeof(ParseShared<true>) <= 10240 ||
-                  (!VCF_ZX_ALIAS && VCF_ZX_LAZYWIN != 3840),
-              "sixteen lazy-parse workgroups per CU");
+static_assert(sizeof(ParseShared<true>) <= 10240, "sixteen lazy-parse workgroups per CU");
 
-#ifdef VCF_ZX_WPE   // A/B (diagnostic builds): registers capped for this many waves per SIMD
-#define VCF_ZX_WPE_ATTR __attribute__((amdgpu_waves_per_eu(VCF_ZX_WPE, VCF_ZX_WPE)))
-#else
-#define VCF_ZX_WPE_ATTR
-#endif
 // The lazy parse's dispatch order: a strip's parse time grows with its literals and
 // short matches, and the last workgroups dispatched form the kernel's tail on an
 // otherwise idle GPU -- so the strips go out longest first (by K1's distinct-hash
@@ -1840,9 +1721,6 @@ static_assert(VCF_ZX_LDSPAD || VCF_ZX_WG != 1 || sizeof(ParseShared<true>) <= 10
 // round's strips by class, descending; position i of the order is stored in strip
 // slot i's workspace (kSumOff + 28).  The order inside a class is whatever the
 // atomics give: it changes only the schedule, never a strip's bytes.
-#ifndef VCF_ZX_LPT   // A/B (diagnostic builds)
-#define VCF_ZX_LPT 1
-#endif
 constexpr int kLptThreads = 1024;
 __device__ __forceinline__ uint32_t lpt_class(uint32_t dsum) { return 255u - min(255u, dsum >> 7); }
 __global__ __launch_bounds__(kLptThreads) void zlib_lpt_kernel(uint8_t *__restrict__ ws, uint32_t cnt)
@@ -1881,14 +1759,8 @@ __device__ __forceinline__ void parse_strip(const uint8_t *__restrict__ in, int6
     ParseSmem &sm = sh.sm;
     const Strip S = strip_of(in, frame_bytes, strip_bytes, spf, ws, s0, s);
     const uint32_t lane = lane_id();
-#ifndef VCF_ZX_PARSEPRIO   // the lazy parse at wave priority 3: beside the side stream's K2b waves on a CU it wins issue (-0.7 %)
-#define VCF_ZX_PARSEPRIO 3
-#endif
-    if (LAZY && VCF_ZX_PARSEPRIO) __builtin_amdgcn_s_setprio(VCF_ZX_PARSEPRIO);
-#if VCF_ZX_LDSZERO   // (diagnostic) LDS cleared first: a read of never-written LDS becomes deterministic
-    for (uint32_t i = lane; i < sizeof(sh) / 4; i += 64) reinterpret_cast<uint32_t *>(&sh)[i] = 0;
-    wave_sync();
-#endif
+    // the lazy parse at wave priority 3: beside the side stream's K2b waves on a CU it wins issue (-0.7 %)
+    if (LAZY) __builtin_amdgcn_s_setprio(3);
     Config cfg;
     level_config(level, cfg);
     for (uint32_t i = lane; i < (uint32_t)kStgWords; i += 64) sm.stg[i] = 0;
@@ -1913,7 +1785,7 @@ __device__ __forceinline__ void parse_strip(const uint8_t *__restrict__ in, int6
         wv.idx = reinterpret_cast<const uint16_t *>(S.ws + kIdxOff);
         wv.sorted = reinterpret_cast<const uint16_t *>(S.ws + kSortOff);
     }
-    if (!LAZY || !VCF_ZX_ALIAS) wv.init_freqs();   // (each flush zeroes them again first)
+    if (!LAZY) wv.init_freqs();   // (LAZY: the window lies over them, and each flush zeroes them first)
     wave_sync();   // the staging words and the window
 
     const uint32_t hdr = zlib_header(level);
@@ -1964,24 +1836,22 @@ __device__ __forceinline__ void parse_strip(const uint8_t *__restrict__ in, int6
 // non-lazy strips returning at once; K3 (!LAZY): the waves loop over K1's list of the
 // round's non-lazy strips
 template <bool LAZY>
-__global__ __launch_bounds__(64 * kParseWG) VCF_ZX_WPE_ATTR void zlib_parse_kernel(
+__global__ __launch_bounds__(64) void zlib_parse_kernel(
     const uint8_t *__restrict__ in, int64_t frame_bytes, int32_t strip_bytes, int32_t spf, int32_t level,
     uint8_t *__restrict__ out, int64_t slot_bytes, int32_t *__restrict__ sizes, uint8_t *__restrict__ ws, int64_t s0,
     int64_t s_end)
 {
-    __shared__ __attribute__((aligned(16))) ParseShared<LAZY> shs[kParseWG];
-    const int wv_id = kParseWG == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    ParseShared<LAZY> &sh = shs[wv_id];
+    __shared__ __attribute__((aligned(16))) ParseShared<LAZY> sh;
     if constexpr (LAZY) {
-        int64_t s = s0 + (int64_t)blockIdx.x * kParseWG + wv_id;
+        int64_t s = s0 + (int64_t)blockIdx.x;
         if (s >= s_end) return;
-        if (VCF_ZX_LPT)   // the longest-first order (zlib_lpt_kernel)
-            s = s0 + *reinterpret_cast<const uint32_t *>(ws + (s - s0) * kWsPerStrip + kSumOff + 28);
+        // the longest-first order (zlib_lpt_kernel)
+        s = s0 + *reinterpret_cast<const uint32_t *>(ws + (s - s0) * kWsPerStrip + kSumOff + 28);
         if (!strip_lazy(strip_of(in, frame_bytes, strip_bytes, spf, ws, s0, s))) return;   // K3 codes this strip
         parse_strip<true>(in, frame_bytes, strip_bytes, spf, level, out, slot_bytes, sizes, ws, s0, s, sh);
     } else {
         const uint32_t cnt = side_count(ws);
-        for (uint32_t i = blockIdx.x * kParseWG + wv_id; i < cnt; i += gridDim.x * kParseWG) {
+        for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x) {
             parse_strip<false>(in, frame_bytes, strip_bytes, spf, level, out, slot_bytes, sizes, ws, s0,
                                s0 + side_strip(ws, i), sh);
             wave_sync();   // the wave's LDS is reused for its next strip
@@ -2086,7 +1956,7 @@ int vcf_zlib_strips(const uint8_t *in_dev, int64_t n_frames, int64_t frame_bytes
     // its workgroups only got a CU when a lazy parse left one
     static hipStream_t side_hi[kMaxDevices] = {};
     const int dev = current_device();
-    if (!VCF_ZX_NOPRIO && !side_hi[dev]) {
+    if (!side_hi[dev]) {
         int least = 0, greatest = 0;
         rc = hip_check(hipDeviceGetStreamPriorityRange(&least, &greatest), "hipDeviceGetStreamPriorityRange");
         if (rc == VCF_OK)
@@ -2095,7 +1965,7 @@ int vcf_zlib_strips(const uint8_t *in_dev, int64_t n_frames, int64_t frame_bytes
         if (rc != VCF_OK) return rc;
     }
     const ZRounds zr(total);
-    const hipStream_t ms = st, ss = VCF_ZX_SERIAL ? st : VCF_ZX_NOPRIO ? ax.s[2] : side_hi[dev];
+    const hipStream_t ms = st, ss = side_hi[dev];
     auto round = [&](int64_t s0, unsigned cnt, uint8_t *ws) -> int {
         int rc0 = hip_check(hipMemsetAsync(ws + kSumOff + 40, 0, 4, ms), "hipMemsetAsync");   // K1's list: empty
         if (rc0 != VCF_OK) return rc0;
@@ -2107,37 +1977,25 @@ int vcf_zlib_strips(const uint8_t *in_dev, int64_t n_frames, int64_t frame_bytes
             if ((rc = hip_check(hipEventRecord(ax.big[0], ms), "hipEventRecord")) != VCF_OK) return rc;
             if ((rc = hip_check(hipStreamWaitEvent(ss, ax.big[0], 0), "hipStreamWaitEvent")) != VCF_OK) return rc;
         }
-#ifdef VCF_ZX_NOSIDE   // diagnostic builds only: no side kernels (wrong output for non-lazy strips)
-        if (false)
-#endif
         hipLaunchKernelGGL(zlib_match_kernel, dim3((unsigned)chunks, std::min(cnt, kSideK2a)), dim3(kK2Threads), 0, ss, in_dev,
                            frame_bytes, strip_bytes, (int32_t)spf, level, ws, s0);
         rc = hip_check(hipGetLastError(), "zlib_match_kernel launch");
-#ifdef VCF_ZX_NOSIDE
-        if (false)
-#endif
         if (rc == VCF_OK) {
             hipLaunchKernelGGL(zlib_chain_kernel, dim3(std::min(cnt, kSideK2b), kK2bSplit), dim3(kK2bThreads), 0, ss, in_dev, frame_bytes,
                                strip_bytes, (int32_t)spf, level, ws, s0);
             rc = hip_check(hipGetLastError(), "zlib_chain_kernel launch");
         }
-#ifdef VCF_ZX_NOSIDE
-        if (false)
-#endif
         if (rc == VCF_OK) {
-            hipLaunchKernelGGL(zlib_parse_kernel<false>, dim3((std::min(cnt, kSideK3) + kParseWG - 1) / kParseWG),
-                               dim3(64 * kParseWG),
-                               0, ss, in_dev, frame_bytes, strip_bytes, (int32_t)spf, level, out_dev, slot_bytes,
+            hipLaunchKernelGGL(zlib_parse_kernel<false>, dim3(std::min(cnt, kSideK3)), dim3(64), 0, ss, in_dev, frame_bytes, strip_bytes, (int32_t)spf, level, out_dev, slot_bytes,
                                sizes_dev, ws, s0, s0 + (int64_t)cnt);
             rc = hip_check(hipGetLastError(), "zlib_parse_kernel launch");
         }
-        if (rc == VCF_OK && VCF_ZX_LPT) {
+        if (rc == VCF_OK) {
             hipLaunchKernelGGL(zlib_lpt_kernel, dim3(1), dim3(kLptThreads), 0, ms, ws, cnt);
             rc = hip_check(hipGetLastError(), "zlib_lpt_kernel launch");
         }
         if (rc == VCF_OK) {
-            hipLaunchKernelGGL(zlib_parse_kernel<true>, dim3((cnt + kParseWG - 1) / kParseWG), dim3(64 * kParseWG),
-                               0, ms, in_dev, frame_bytes, strip_bytes, (int32_t)spf, level, out_dev, slot_bytes,
+            hipLaunchKernelGGL(zlib_parse_kernel<true>, dim3(cnt), dim3(64), 0, ms, in_dev, frame_bytes, strip_bytes, (int32_t)spf, level, out_dev, slot_bytes,
                                sizes_dev, ws, s0, s0 + (int64_t)cnt);
             rc = hip_check(hipGetLastError(), "zlib_parse_kernel (lazy) launch");
         }

@@ -1297,20 +1297,6 @@ int check_dwt(const void *a, const void *b, int64_t n_frames, int32_t H, int32_t
 
 unsigned gx(int n) { return (unsigned)((n + 255) / 256); }
 
-// The kernel schedule of one call; the defaults are the library's rules.  The
-// product entry points pass DwtSchedule{}; the A/B library's vcf_dwt_dz_*_sched
-// (ab/vcf_dwt_sched.hip, include/vcf_amd_ab.h) pass a caller's.  Every setting
-// gives the same bytes.
-struct DwtSchedule {
-    int enc_bands = 0;        // bands of the level 1 + 2 kernel (0 = the cost model)
-    int dec_line_bands = 0;   // bands of each inverse line launch (0 = the cost model)
-    int dec21_brows = 0;      // level-1 rows per band of the inverse levels 2 + 1 kernel (0 = its rule)
-    int enc_pipe = -1;        // the encode as a frame pipeline: -1 = the rule, 0 off, 1 on where pipeline_default
-    int dec_pipe = -1;        // the decode likewise (the rule: off)
-    int band21 = 1;           // inverse levels 2 and 1 in one launch where band21_ok
-    int lift_fused = 1;       // the lifting form's level pairs in one launch
-};
-
 // resident workgroups of one kernel on the current device: its CUs x the
 // `threads`-wide workgroups of kern that fit one (fallback_per_cu where the
 // query fails; kern == nullptr: fallback_per_cu is the count), cached per
@@ -1775,7 +1761,6 @@ using namespace vcf;
 
 extern "C" {
 
-#ifndef VCF_DWT_SCHED_BUILD   // (the A/B library has these from ab/vcf_dwt_ab.hip)
 int vcf_wavelet_index(const char *name, int32_t *index)
 {
     if (!name || !index) return set_error(VCF_ERR_INVALID, "null pointer");
@@ -1801,7 +1786,8 @@ int vcf_dwt_layout(int32_t H, int32_t W, int32_t levels, int32_t *sub_h, int32_t
     if (workspace_bytes_per_frame) *workspace_bytes_per_frame = 3 * plane_doubles(g) * (int64_t)sizeof(double);
     return VCF_OK;
 }
-#endif
+
+}  // extern "C"
 
 // one stream's level chain of the encode (the frame pipeline calls it per
 // chunk of frames with its hook).  Levels: 1 and 2 in one band launch when
@@ -1866,9 +1852,8 @@ static void dwt_plan(const DwtGeom &g, const WaveletDef &wd, const DwtSchedule &
     }
 }
 
-#ifndef VCF_DWT_SCHED_BUILD
-int vcf_dwt_plan(int32_t H, int32_t W, int32_t wavelet, int32_t levels, int64_t n_frames, int32_t *enc_kind,
-                 int32_t *enc_ct, int32_t *dec_kind, int32_t *dec_ct)
+extern "C" int vcf_dwt_plan(int32_t H, int32_t W, int32_t wavelet, int32_t levels, int64_t n_frames,
+                            int32_t *enc_kind, int32_t *enc_ct, int32_t *dec_kind, int32_t *dec_ct)
 {
     if (!enc_kind || !enc_ct || !dec_kind || !dec_ct) return set_error(VCF_ERR_INVALID, "null pointer");
     const int rc = check_dwt(nullptr, nullptr, 0, H, W, wavelet, levels, 1, false);
@@ -1886,7 +1871,6 @@ int vcf_dwt_plan(int32_t H, int32_t W, int32_t wavelet, int32_t levels, int64_t 
     }
     return VCF_OK;
 }
-#endif
 
 static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                         int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, hipStream_t s,
@@ -1951,8 +1935,8 @@ static int encode_chain(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int
     return VCF_OK;
 }
 
-static int dwt_encode(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
-                      int32_t wavelet, int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
+int vcf::dwt_encode(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
+                    int32_t wavelet, int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
 {
     int rc = check_dwt(rgb_dev, packed_dev, n_frames, H, W, wavelet, levels, Q, false);
     if (rc != VCF_OK) return rc;
@@ -2030,8 +2014,8 @@ static int decode_chain_fast(const uint8_t *packed_dev, int64_t n_frames, int32_
 // sc.dec_pipe = 1 selects it for A/B.
 constexpr PipeShape kDecodePipe{2, 2, false};
 
-static int dwt_decode(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
-                      int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
+int vcf::dwt_decode(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
+                    int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream)
 {
     int rc = check_dwt(packed_dev, rgb_dev, n_frames, H, W, wavelet, levels, Q, true);
     if (rc != VCF_OK) return rc;
@@ -2090,9 +2074,9 @@ static int dwt_decode(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t 
 
 // The lifting path (vcf_dwt_lift.h): bior4.4 only, same buffers, layout and
 // workspace as vcf_dwt_dz_encode / _decode; results within +-1 of theirs.
-static int dwt_encode_lift(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
-                           int32_t wavelet, int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev,
-                           void *stream)
+int vcf::dwt_encode_lift(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
+                         int32_t wavelet, int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev,
+                         void *stream)
 {
     int rc = check_dwt(rgb_dev, packed_dev, n_frames, H, W, wavelet, levels, Q, false);
     if (rc != VCF_OK || (rc = lift_check(wavelet)) != VCF_OK) return rc;
@@ -2177,9 +2161,8 @@ static int dwt_encode_lift(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_
 // level; coef_dev receives, per level l = 1..levels, the details [LH, HL, HH][Y, Co,
 // Cg][hs[l] x ws[l]], then LL_levels [Y, Co, Cg][hs x ws]; packed_dev (the packed
 // layout's bytes) receives Q = 1 indices as scratch.
-#ifndef VCF_DWT_SCHED_BUILD
-int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32_t levels, double *coef_dev,
-                             uint8_t *packed_dev, void *workspace_dev, void *stream)
+extern "C" int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32_t levels,
+                                        double *coef_dev, uint8_t *packed_dev, void *workspace_dev, void *stream)
 {
     int32_t wavelet = 0;
     int rc = vcf_wavelet_index("bior4.4", &wavelet);
@@ -2216,11 +2199,10 @@ int vcf_dwt_lift_analyze_f64(const uint8_t *rgb_dev, int32_t H, int32_t W, int32
             return rc;
     return VCF_OK;
 }
-#endif
 
-static int dwt_decode_lift(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
-                           int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev,
-                           void *stream)
+int vcf::dwt_decode_lift(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
+                         int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev,
+                         void *stream)
 {
     int rc = check_dwt(packed_dev, rgb_dev, n_frames, H, W, wavelet, levels, Q, true);
     if (rc != VCF_OK || (rc = lift_check(wavelet)) != VCF_OK) return rc;
@@ -2294,7 +2276,8 @@ static int dwt_decode_lift(const DwtSchedule &sc, const uint8_t *packed_dev, int
     return VCF_OK;
 }
 
-#ifndef VCF_DWT_SCHED_BUILD
+extern "C" {
+
 // the product entry points: the library's schedule
 int vcf_dwt_dz_encode(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
                       int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream)
@@ -2319,7 +2302,6 @@ int vcf_dwt_dz_decode_lift(const uint8_t *packed_dev, int64_t n_frames, int32_t 
 {
     return dwt_decode_lift(DwtSchedule{}, packed_dev, n_frames, H, W, wavelet, levels, Q, rgb_dev, workspace_dev, stream);
 }
-#endif
 
 }  // extern "C"
 #endif  // VCF_DWT_KERNELS_ONLY

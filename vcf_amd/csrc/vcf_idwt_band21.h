@@ -33,9 +33,6 @@
 constexpr int kB21C = 60;            // owned level-1 subband columns per tile (64 lanes, 2 halo each side)
 constexpr int kB21S2 = 36;           // staged level-2 subband columns per row
 constexpr int kB21NT = 192;          // one wave per YCoCg channel
-#ifndef VCF_B21_SPLIT   // (A/B) the level-1 row pass's two halves kept apart: fewer live VGPRs
-#define VCF_B21_SPLIT 1
-#endif
 
 template <bool FROM_PACKED_LL2, unsigned ZLO, unsigned ZHI, int CT, bool QS>
 __global__ __launch_bounds__(kB21NT) void idwt_band21_kernel(
@@ -232,7 +229,8 @@ __global__ __launch_bounds__(kB21NT) void idwt_band21_kernel(
                     double(&o)[5][2] = half ? wd : wa;
                     o[u][0] = inv_pair<ZLO, ZHI, CT, 0>(x, y);
                     o[u][1] = inv_pair<ZLO, ZHI, CT, 1>(x, y);
-                    if (VCF_B21_SPLIT) asm volatile("" ::: "memory");   // the 'd' loads after the 'a' sums
+                    // the 'd' loads after the 'a' sums: the two halves kept apart, fewer live VGPRs
+                    asm volatile("" ::: "memory");
                 }
             }
             // level-1 column pass: output pair m = r - 2 from rows r - 4 .. r

@@ -92,4 +92,27 @@ int cbaac_tiled_decode_classes(int32_t kernel, const uint8_t *in_dev, const int6
 // Block matching (vcf_ipp.hip), variant: 0 = the word kernels where the block size allows, 1 = the byte kernels
 int ipp_block_match(int32_t variant, const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W,
                     int32_t bs, int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream);
+
+// The kernel schedule of one 2D-DWT call (vcf_dwt.hip); the defaults are the library's rules.  The
+// product entry points pass DwtSchedule{}; the A/B library's vcf_dwt_dz_*_sched twins
+// (ab/vcf_dwt_sched.hip, include/vcf_amd_ab.h) pass a caller's.  Every setting gives the same bytes.
+struct DwtSchedule {
+    int enc_bands = 0;        // bands of the level 1 + 2 kernel (0 = the cost model)
+    int dec_line_bands = 0;   // bands of each inverse line launch (0 = the cost model)
+    int dec21_brows = 0;      // level-1 rows per band of the inverse levels 2 + 1 kernel (0 = its rule)
+    int enc_pipe = -1;        // the encode as a frame pipeline: -1 = the rule, 0 off, 1 on where pipeline_default
+    int dec_pipe = -1;        // the decode likewise (the rule: off)
+    int band21 = 1;           // inverse levels 2 and 1 in one launch where band21_ok
+    int lift_fused = 1;       // the lifting form's level pairs in one launch
+};
+int dwt_encode(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t wavelet,
+               int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev, void *stream);
+int dwt_decode(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
+               int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev, void *stream);
+int dwt_encode_lift(const DwtSchedule &sc, const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W,
+                    int32_t wavelet, int32_t levels, int32_t Q, uint8_t *packed_dev, void *workspace_dev,
+                    void *stream);
+int dwt_decode_lift(const DwtSchedule &sc, const uint8_t *packed_dev, int64_t n_frames, int32_t H, int32_t W,
+                    int32_t wavelet, int32_t levels, int32_t Q, uint8_t *rgb_dev, void *workspace_dev,
+                    void *stream);
 }  // namespace vcf

@@ -126,7 +126,7 @@ def decode_device(packed: DeviceBuffer, n: int, H: int, W: int, wavelet: int, le
 def _run(name: str, variant: int, lifting: bool, schedule, *args) -> None:
     """The product entry point `name` (its lifting form), or the A/B library's
     variant of it, or -- schedule: a mapping of vcf_dwt_schedule's field names
-    (include/vcf_amd_ab.h) -- the A/B library's build of the product code under
+    (include/vcf_amd_ab.h) -- the A/B library's twin of it, the product code under
     that kernel schedule (A/B records and cross-checks, not the product path;
     unknown field names raise ValueError before the call)."""
     if variant and (lifting or schedule is not None):
