@@ -31,7 +31,10 @@
  *     Hp, Wp = H, W rounded up to the block size (vcf_dct_padded_shape): the
  *     array the reference hands to its entropy codec (2D-DCT.py:364).
  *   - Work is enqueued on `stream` (a hipStream_t, NULL = default stream)
- *     and is asynchronous; synchronise with vcf_stream_sync.
+ *     and is asynchronous; synchronise with vcf_stream_sync.  A call may run
+ *     part of its work on library-owned streams, forked from and joined to
+ *     `stream`, and may block the host while a workspace the library shares
+ *     between calls grows.
  *   - Alignment and extents.  A byte-typed frame pointer (uint8_t *: images,
  *     index frames, luma workspaces) needs no alignment: a pointer into the
  *     middle of a larger allocation gives the same bytes, the kernels taking
