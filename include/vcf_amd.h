@@ -1039,6 +1039,44 @@ int vcf_ssim_tile(void);
 int vcf_index_hist_u8(const uint8_t *idx_dev, int64_t n_frames, int32_t H, int32_t W, int32_t rows, int32_t cols,
                       uint32_t *counts_dev, int64_t counts_capacity, void *stream);
 
+/* ---- rate-distortion optimised quantization of the 8x8 DCT encode (vcf_amd/rdoq.py) ----
+ *
+ * vcf_dct_dz_encode with one more step per coefficient: where the bits saved are
+ * worth more than the distortion added, an index is lowered towards zero.  Input,
+ * output, padding and layouts (VCF_DCT_NO_SUBBANDS) are vcf_dct_dz_encode's, and
+ * the output is an ordinary index frame: every decoder reads it.  Encoder side
+ * only, and not in the reference.
+ *
+ * cost_dev: float64 [cost_frames][64][3][256], cost_frames = 1 (one table for
+ * every frame) or n_frames; entry [f][8 i + j][ch][(k + 128) & 255] is the cost
+ * in bits of index k at row i, column j of a block in channel ch of frame f (the
+ * position in the block, in both layouts).  For a coefficient c (the float32
+ * value vcf_dct_dz_encode divides by Q) with deadzone index k0 = trunc(c / Q),
+ * s = sign(k0), and
+ *     J(k) = d * d + lambda * cost[..][(k + 128) & 255],  d = (double)c - (double)(Q * k),
+ * in float64, every operation rounded on its own:
+ *   1. k0 == 0, k0 < -128 or k0 > 127: the index is k0 (and wraps modulo 256 as in
+ *      vcf_dct_dz_encode);
+ *   2. otherwise best = k0; k0 - s replaces it if J(k0 - s) <= J(best); then, if
+ *      k0 - s != 0, 0 replaces it if J(0) <= J(best);
+ *   3. the byte is (best + 128) & 255.
+ * So no magnitude grows, lambda = 0 gives vcf_dct_dz_encode's bytes, and the sum of
+ * J under a given table is never above the plain encode's.
+ *
+ * block_size != 8 and VCF_DCT_PERCEPTUAL: VCF_ERR_UNSUPPORTED.  A null pointer,
+ * n_frames < 1, cost_frames other than 1 or n_frames, cost_capacity (doubles at
+ * cost_dev) below cost_frames * 64 * 3 * 256, a cost_dev off 8 bytes, a lambda that
+ * is negative or not finite, Q < 1: VCF_ERR_INVALID; all before any device work,
+ * nothing written.  rgb_dev and k_dev need no alignment, as for vcf_dct_dz_encode;
+ * writes the n_frames * Hp * Wp * 3 bytes at k_dev and reads the table in place.
+ * The work is enqueued on `stream`; the call keeps no state.  Batches of more than
+ * 65535 frames run in launches of 65535. */
+int vcf_dct_dz_encode_rdoq(const uint8_t *rgb_dev, int64_t n_frames, int32_t H, int32_t W, int32_t block_size,
+                           int32_t Q, uint32_t flags, const double *cost_dev, int64_t cost_frames,
+                           int64_t cost_capacity, double lambda, uint8_t *k_dev, void *stream);
+/* The blocks one workgroup of vcf_dct_dz_encode_rdoq takes (for tests and benchmarks). */
+int vcf_dct_rdoq_tile(void);
+
 /* ---- cross-rank exchange on RCCL over xGMI -------------------
  * Frames shard across one process per GPU with no collective on the data
  * path; the one exchange step of the III / IPP drivers is after coding: an

@@ -131,6 +131,8 @@ SIGNATURES = {
     "vcf_ssim_u8": [_P, _P, _I64, _I32, _I32, _I32, _P, _P],
     "vcf_ssim_tile": [],
     "vcf_index_hist_u8": [_P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P],
+    "vcf_dct_dz_encode_rdoq": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _I64, _I64, ctypes.c_double, _P, _P],
+    "vcf_dct_rdoq_tile": [],
     "vcf_wavelet_index": [ctypes.c_char_p, _PI32],
     "vcf_dwt_layout": [_I32, _I32, _I32, _PI32, _PI32, ctypes.POINTER(_I64), ctypes.POINTER(_I64)],
     "vcf_dwt_plan": [_I32, _I32, _I32, _I32, _I64, _PI32, _PI32, _PI32, _PI32],

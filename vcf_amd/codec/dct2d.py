@@ -62,6 +62,7 @@ class CoDec(BlockCoDec):
     FRAME_ERROR = "Input image must be a 3D array (height, width, channels)."
 
     def __init__(self, args):
+        self.rdoq = self._rdoq_option(args)
         super().__init__(args)
         self.Lambda = None
         if self.encoding and getattr(args, "Lambda", None) is not None and self.lm is not None:
@@ -75,6 +76,32 @@ class CoDec(BlockCoDec):
                 logging.info(f"optimal block_size={self.block_size}")
             else:
                 logging.warning("sorry, perceptual quantization is only available for block_size=8")
+
+    @staticmethod
+    def _rdoq_option(args):
+        """--rdoq MU (encode only, not in the reference): None, or MU after the refusals -- the RDOQ
+        kernel is the 8x8 deadzone one without -p, and -L's search codes with the plain quantizer."""
+        mu = getattr(args, "rdoq", None)
+        if mu is None or getattr(args, "subparser_name", None) != "encode":
+            return None
+        mu = float(mu)
+        if not np.isfinite(mu) or mu < 0:
+            raise ValueError(f"--rdoq {mu}: a finite value >= 0")
+        if int(getattr(args, CoDec.BLOCK_SIZE_ARG, 8)) != 8:
+            raise NotImplementedError("--rdoq with -B other than 8: the RDOQ encode has the 8x8 kernel only")
+        if getattr(args, "perceptual_quantization", False):
+            raise NotImplementedError("--rdoq with -p: the RDOQ encode has no perceptual quantization")
+        if getattr(args, "Lambda", None) is not None:
+            raise NotImplementedError("--rdoq with -L: the block-size search codes with the plain quantizer")
+        if getattr(args, "quantizer", "deadzone") != "deadzone":
+            raise NotImplementedError(f"--rdoq with -a {args.quantizer}: RDOQ decides deadzone indices")
+        return mu
+
+    def _rdoq_indices(self, frames):
+        """The two-pass RDOQ pipeline (vcf_amd/rdoq.py) on one frame or a batch of equal shapes:
+        one cost table per frame, lambda = MU * q * q."""
+        from .. import rdoq as R
+        return R.encode(frames, self.QSS, R.lambda_of(self.rdoq, self.QSS), self.flags)
 
     def bye(self):
         st = getattr(self, "_staged", None)
@@ -195,6 +222,8 @@ class CoDec(BlockCoDec):
         self._deadzone_only("encode_indices")
         self._check_frame(img)
         self.original_shape = img.shape
+        if self.rdoq is not None:
+            return self._rdoq_indices(img)
         return D.encode(img, self.QSS, self.flags, self.block_size)
 
     def decode_indices(self, k: np.ndarray, shape) -> np.ndarray:
@@ -207,7 +236,7 @@ class CoDec(BlockCoDec):
     def _encode_one(self, img):
         if self.lm is not None:
             return self.compress(self.encode_lm(img)), None
-        if hasattr(self.entropy, "compress_device"):
+        if hasattr(self.entropy, "compress_device") and self.rdoq is None:
             return self._encode_compress_device(img), None
         return self.compress(self.encode_indices(img)), None
 
@@ -240,10 +269,14 @@ class CoDec(BlockCoDec):
 
     # ---- batched frames (III runner) ------------------------------------------
     def _encode_group(self, frames, shape):
+        if self.rdoq is not None:
+            return [(k, None) for k in self._rdoq_indices(frames)]
         return [(k, None) for k in D.encode(frames, self.QSS, self.flags, self.block_size)]
 
     def _encode_fns_staged(self, pairs, batch, io_threads):
         from .. import staging
+        if self.rdoq is not None:      # the ordinary batched path: a table per frame between two encodes
+            return None
         probes = [staging.png_probe(p[0]) if p[0].lower().endswith(".png") else None for p in pairs]
         if any(pr is None or not pr[2] for pr in probes) or len({pr[:2] for pr in probes}) != 1:
             return None

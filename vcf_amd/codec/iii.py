@@ -98,6 +98,12 @@ class CoDec:
         if self.rate_control or self.q_from_files:
             from . import ratecontrol
             ratecontrol.refuse_unless_dct(args, getattr(args, "transform", "2D-DCT"))
+        if self.encoding and getattr(args, "rdoq", None) is not None:      # --rdoq (not in the reference)
+            if getattr(args, "transform", "2D-DCT") != "2D-DCT":
+                raise NotImplementedError(f"--rdoq with -T {args.transform}: RDOQ is the 2D-DCT encode's")
+            if self.rate_control:
+                raise NotImplementedError("--rdoq with --target_bpp / --target_bytes: the rate control probes the "
+                                          "plain quantizer")
         self.transform_codec = codec if codec is not None else transform_codec(args)
         self.batch = batch
         self.encode_prefix = encode_prefix

@@ -252,12 +252,23 @@ def add_iii(enc, dec):
                        help=f"Number of frames to {what} (default: {N_FRAMES})", default=f"{N_FRAMES}")
 
 
+def add_rdoq(enc):
+    """Not in the reference: rate-distortion optimised quantization of the 2D-DCT encode
+    (vcf_amd/rdoq.py).  Encoder side only: the files are ordinary -q files."""
+    enc.add_argument("--rdoq", type=float, default=None, metavar="MU",
+                     help="Lower an index towards zero where that saves more bits than it costs distortion: "
+                          "lambda = MU * q * q, MU >= 0 (default: off)")
+
+
 def dct_parser(description: str = "Exploiting spatial redundancy with the 2D Discrete Cosine "
                                   "Transform of constant block size.", quantizer: str = DEFAULT_QUANTIZER,
-               entropy: str = DEFAULT_EIC):
-    """The parser `python 2D-DCT.py ...` ends up with (the codec chain -a and -c name)."""
+               entropy: str = DEFAULT_EIC, rdoq: bool = False):
+    """The parser `python 2D-DCT.py ...` ends up with (the codec chain -a and -c name).  rdoq adds
+    --rdoq, as 2D-DCT.py does; without it the Namespace is the reference's."""
     p, enc, dec = base_parser(description)
     add_dct(enc, dec)
+    if rdoq:
+        add_rdoq(enc)
     add_ycocg(enc, dec)
     add_quantizer(enc, dec, quantizer)
     add_filter(enc, dec, entropy)
@@ -343,14 +354,17 @@ def rate_control_parser(description: str = "2D-DCT coding under a byte budget: -
 
 
 def iii_parser(description: str = "III coding: runs a 2D image codec for each image of a sequence.",
-               transform: str = "2D-DCT", entropy: str = DEFAULT_EIC, rate_control: bool = False):
+               transform: str = "2D-DCT", entropy: str = DEFAULT_EIC, rate_control: bool = False,
+               rdoq: bool = False):
     """`python III.py ...` (III.py + the chain of the 2D codec it imports).  rate_control adds
-    --target_bpp, --target_bytes and --q_from_files, as III.py does; without it the Namespace is
-    the reference's."""
+    --target_bpp, --target_bytes and --q_from_files, rdoq adds --rdoq, as III.py does; without
+    them the Namespace is the reference's."""
     p, enc, dec = base_parser(description)
     add_iii(enc, dec)
     if rate_control:
         add_rate_control(enc, dec)
+    if rdoq:
+        add_rdoq(enc)
     if transform == "2D-DWT":
         add_dwt(enc, dec)
     elif transform == "2D-MDCT":
@@ -500,9 +514,11 @@ def rde_parser(description: str = "Compute the rate/distortion efficiency (J=R+D
 def rd_curve_parser(description: str = "Rate-distortion curve of the default chain (2D-DCT, YCoCg, deadzone, "
                                        "TIFF) with the frames resident on the GPU. This program has no "
                                        "counterpart in the reference: it replaces a loop of 2D-DCT.py encode, "
-                                       "2D-DCT.py decode and RDE.py over -q values."):
-    """`python RD-curve.py ...`: -B, -p and -x as 2D-DCT.py names them."""
+                                       "2D-DCT.py decode and RDE.py over -q values.", rdoq: bool = False):
+    """`python RD-curve.py ...`: -B, -p and -x as 2D-DCT.py names them; rdoq adds --rdoq."""
     p = argparse.ArgumentParser(description=description)
+    if rdoq:
+        add_rdoq(p)
     p.add_argument("-o", "--original", type=str, default=ORIGINAL,
                    help="Input image; with -N a printf pattern of the frame number; or an .npy file holding "
                         "N x H x W x 3 uint8 frames (default: %(default)s)")

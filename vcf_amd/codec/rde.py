@@ -254,7 +254,7 @@ def _hwc(a: np.ndarray):
     return a.shape if a.ndim == 3 else a.shape + (1,)
 
 
-def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False) -> list:
+def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False, rdoq=None) -> list:
     """The rate-distortion curve of the default chain (2D-DCT.py: YCoCg, B x B DCT, deadzone, -c TIFF) over the
     quantization steps Qs, with the n equal-shape H x W x 3 u8 frames uploaded once.  Per Q, on the device:
     dct.encode_device, the deflate of the TIFF strips for their sizes (zlib_gpu.tiff_sizes_device), dct.decode_device
@@ -265,9 +265,14 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False
     resident originals against the resident reconstructions, measured by vcf_ssim_u8 right after the distortion;
     only its records come back too.  Frames under 11 x 11 then raise ValueError.  Raises NotImplementedError where
     the GPU deflate does not cover the frame (rows over 64 KB): the host TIFF writer's sizes would be the same, but a
-    silent change of path is not this function's to make."""
+    silent change of path is not this function's to make.  rdoq = MU codes the indices with the two-pass RDOQ
+    pipeline (vcf_amd/rdoq.py, lambda = MU * Q * Q; B = 8 without -p only) instead of the plain encode: the same
+    curve, to be read against the plain one at equal Q or at equal bytes."""
     from .. import dct as D
+    from .. import rdoq as R
     from .. import zlib_gpu
+    if rdoq is not None and (block_size != 8 or flags & D.VCF_DCT_PERCEPTUAL):
+        raise NotImplementedError("--rdoq: the RDOQ encode has the 8x8 kernel without -p only")
     f = np.asarray(frames)
     if f.dtype != np.uint8:
         raise TypeError(f"frames must be uint8, got {f.dtype}")
@@ -298,7 +303,11 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False
         curve = []
         for Q in Qs:
             Q = int(Q)
-            D.encode_device(src, n, H, W, Q, flags, out=k, stream=st, block_size=block_size)
+            if rdoq is None:
+                D.encode_device(src, n, H, W, Q, flags, out=k, stream=st, block_size=block_size)
+            else:     # the pipeline works on the null stream and ends synchronised
+                st.synchronize()
+                R.encode_frames_device(src, n, H, W, Q, R.lambda_of(rdoq, Q), flags, out=k)
             tif = zlib_gpu.tiff_sizes_device(k, n, (Hp, Wp, 3), np.uint8, stream=st)
             D.decode_device(k, n, H, W, Q, flags, out=rec, stream=st, block_size=block_size)
             DS.sse_device(src, rec, n, H, W, 3, out, st)
@@ -352,18 +361,19 @@ def _curve_frames(original: str, n):
 
 
 def curve_main(argv=None) -> int:
-    """`python RD-curve.py -o ... -q 8,16,32 [-N n] [-B b] [-p] [-x] [--ssim] [--json]`."""
+    """`python RD-curve.py -o ... -q 8,16,32 [-N n] [-B b] [-p] [-x] [--ssim] [--rdoq MU] [--json]`."""
     import json
     import sys
 
     from .. import dct as D
     from . import parser as P
-    args = P.rd_curve_parser().parse_args(argv)
+    args = P.rd_curve_parser(rdoq=True).parse_args(argv)
     Qs = [int(q) for q in str(args.QSS).split(",") if q.strip()]
     frames = _curve_frames(args.original, args.number_of_frames)
     try:
         curve = rd_curve(frames, Qs, int(args.block_size_DCT),
-                         D.flags_from(args.disable_subbands, args.perceptual_quantization), ssim=args.ssim)
+                         D.flags_from(args.disable_subbands, args.perceptual_quantization), ssim=args.ssim,
+                         rdoq=args.rdoq)
     except DS.SsimShapeError as e:
         print(f"RD: {e}", file=sys.stderr)
         return 1

@@ -636,9 +636,13 @@ VCF_HD void fold_columns(const uint32_t (&raw)[8][6], uint32_t magic, const Fina
     }
 }
 
+// encode_block_channel_fold_q hands the sink the quotient itself, sink(i, j, t, q): q is what is
+// truncated to the index, t the transform's output that was divided (t == q for a power-of-two Q;
+// otherwise t = c * 2^e, e = qexp<C>(i, j), of the coefficient c in the reference's units);
+// encode_block_channel_fold is that with the truncation as the sink.
 template <int C, bool POW2, bool PERC, bool SDWA = false, typename Sink>
-VCF_HD void encode_block_channel_fold(const uint32_t (&raw)[8][6], const FinalK &rowk, const float (&qd)[4],
-                                      Sink &&sink)
+VCF_HD void encode_block_channel_fold_q(const uint32_t (&raw)[8][6], const FinalK &rowk, const float (&qd)[4],
+                                        Sink &&sink)
 {
     // column pass: 2^-(chs + inv(i)), chs = log2 of the channel scale (4Y, 2Co, 4Cg)
     constexpr float cs = C == 1 ? 0.5f : 0.25f;
@@ -659,9 +663,17 @@ VCF_HD void encode_block_channel_fold(const uint32_t (&raw)[8][6], const FinalK 
             float t = v[i][j];
             if (PERC) t = (float)((double)t * pweight<C>(i * 8 + j));
             const float q = POW2 ? t : quant_div<false>(t, qd[qexp<C>(i, j) - 3]);
-            sink(i, j, (uint32_t)cvt_trunc_i32(q));
+            sink(i, j, t, q);
         }
     }
+}
+
+template <int C, bool POW2, bool PERC, bool SDWA = false, typename Sink>
+VCF_HD void encode_block_channel_fold(const uint32_t (&raw)[8][6], const FinalK &rowk, const float (&qd)[4],
+                                      Sink &&sink)
+{
+    encode_block_channel_fold_q<C, POW2, PERC, SDWA>(
+        raw, rowk, qd, [&](int i, int j, float, float q) { sink(i, j, (uint32_t)cvt_trunc_i32(q)); });
 }
 
 // ---- provably zero rows of the row pass (power-of-two Q, no -p) -----------
@@ -795,8 +807,11 @@ VCF_HD void fold_columns_pk(const uint32_t (&raw)[8][6], uint32_t magic, const F
 // wave-uniform.  1: the sink still gets the skipped pair's 16 zero indices;
 // 2: it gets nothing (the caller has zeroed rows 2..7 of its image).  Row
 // pair 0 carries DC and is always computed.
+// encode_block_channel_pk_q hands the sink the quotient q = c / Q itself, sink(i, j, q), whose
+// truncation is the index (a skipped pair's, under SKIP == 1, is +0); encode_block_channel_pk is
+// that with the truncation as the sink.
 template <int C, int SKIP = 0, typename Sink>
-VCF_HD void encode_block_channel_pk(const uint32_t (&raw)[8][6], const FinalK &rowk, float dep0, Sink &&sink)
+VCF_HD void encode_block_channel_pk_q(const uint32_t (&raw)[8][6], const FinalK &rowk, float dep0, Sink &&sink)
 {
     constexpr float cs = C == 1 ? 0.5f : 0.25f;
     constexpr FinalK colk = final_k(cs * 0.25f, cs * 0.5f);
@@ -816,8 +831,8 @@ VCF_HD void encode_block_channel_pk(const uint32_t (&raw)[8][6], const FinalK &r
                 if (SKIP == 1) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        sink(2 * p, j, 0u);
-                        sink(2 * p + 1, j, 0u);
+                        sink(2 * p, j, 0.0f);
+                        sink(2 * p + 1, j, 0.0f);
                     }
                 }
                 continue;
@@ -834,10 +849,17 @@ VCF_HD void encode_block_channel_pk(const uint32_t (&raw)[8][6], const FinalK &r
         dep = r[0];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            sink(2 * p, j, (uint32_t)cvt_trunc_i32(r[j].x));
-            sink(2 * p + 1, j, (uint32_t)cvt_trunc_i32(r[j].y));
+            sink(2 * p, j, r[j].x);
+            sink(2 * p + 1, j, r[j].y);
         }
     }
+}
+
+template <int C, int SKIP = 0, typename Sink>
+VCF_HD void encode_block_channel_pk(const uint32_t (&raw)[8][6], const FinalK &rowk, float dep0, Sink &&sink)
+{
+    encode_block_channel_pk_q<C, SKIP>(raw, rowk, dep0,
+                                       [&](int i, int j, float q) { sink(i, j, (uint32_t)cvt_trunc_i32(q)); });
 }
 #endif
 
