@@ -1014,6 +1014,40 @@ int vcf_ssim_u8(const uint8_t *a_dev, const uint8_t *b_dev, int64_t n_frames, in
 /* The edge, in windows, of the square tile one workgroup of vcf_ssim_u8 takes (for tests and benchmarks). */
 int vcf_ssim_tile(void);
 
+/* ---- deblocking post-filter of the block-transform decoders ------
+ *
+ * Not in the reference.  in_dev holds n_frames decoded frames of H x W x 3 uint8
+ * (channel fastest), frame f at in_dev + f * frame_stride_bytes; out_dev receives
+ * the filtered frames at the same stride.  Every channel is filtered on its own.
+ * All arithmetic is int32, >> is an arithmetic shift, clip255 saturates to 0..255.
+ * The block grid has period B and starts `left` columns and `top` rows outside
+ * the frame (what the decoder cropped): a vertical edge lies between columns
+ * x - 1 and x iff 0 < x < W and (x + left) % B == 0, a horizontal one between
+ * rows y - 1 and y iff 0 < y < H and (y + top) % B == 0.
+ *   Pass V, vertical edges, along rows, every read from the input: per edge x, row
+ *     and channel, p2 p1 p0 = in[x-3] in[x-2] in[x-1], q0 q1 q2 = in[x] in[x+1]
+ *     in[x+2]; a line with x - 3 < 0 or x + 2 > W - 1 is left as it is.
+ *   Pass H, horizontal edges, the same rule down columns, reading pass V's result.
+ *   Per line:  dp = |p2 - 2 p1 + p0|, dq = |q2 - 2 q1 + q0|; unchanged if
+ *     dp + dq >= beta.  delta = (9 (q0 - p0) - 3 (q1 - p1) + 8) >> 4; unchanged if
+ *     |delta| >= 10 tc.  delta = clip(-tc, tc, delta); p0' = clip255(p0 + delta),
+ *     q0' = clip255(q0 - delta).  side = (beta + (beta >> 1)) >> 3, h = tc >> 1;
+ *     if dp < side: p1' = clip255(p1 + clip(-h, h, (((p2 + p0 + 1) >> 1) - p1 + delta) >> 1));
+ *     if dq < side: q1' = clip255(q1 + clip(-h, h, (((q2 + q0 + 1) >> 1) - q1 - delta) >> 1)).
+ *     p2 and q2 are never written.  (HEVC's normal filter, decided per line.)
+ * With B >= 4 no two lines of a pass write the same sample.  A frame without an
+ * interior edge is copied.  Only the H * W * 3 bytes of each frame are written;
+ * the bytes between frames that frame_stride_bytes leaves are not touched.  The
+ * frames need no alignment (where out_dev - in_dev is a multiple of 16 the stores
+ * are 16 bytes wide, otherwise bytes).  Out of place: in_dev == out_dev or
+ * overlapping extents, B < 4, top or left outside [0, B), negative beta, tc or
+ * size, frame_stride_bytes < H * W * 3, a null pointer: VCF_ERR_INVALID before
+ * any device work.  n_frames = 0 or H * W = 0: VCF_OK and nothing is enqueued.
+ * Otherwise one kernel per 65535 frames is enqueued on `stream`; no workspace. */
+int vcf_deblock_u8(const uint8_t *in_dev, uint8_t *out_dev, int64_t n_frames, int32_t H, int32_t W,
+                   int64_t frame_stride_bytes, int32_t B, int32_t top, int32_t left, int32_t beta, int32_t tc,
+                   void *stream);
+
 /* ---- histograms of index planes (the rate estimate of vcf_amd/rate.py) -----------
  *
  * idx_dev holds n_frames contiguous index frames of H x W x 3 uint8 (channel

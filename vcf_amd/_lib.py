@@ -130,6 +130,7 @@ SIGNATURES = {
     "vcf_distortion_u8": [_P, _P, _I64, _I32, _I32, _I32, _P, _P],
     "vcf_ssim_u8": [_P, _P, _I64, _I32, _I32, _I32, _P, _P],
     "vcf_ssim_tile": [],
+    "vcf_deblock_u8": [_P, _P, _I64, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _P],
     "vcf_index_hist_u8": [_P, _I64, _I32, _I32, _I32, _I32, _P, _I64, _P],
     "vcf_dct_dz_encode_rdoq": [_P, _I64, _I32, _I32, _I32, _I32, _U32, _P, _I64, _I64, ctypes.c_double, _P, _P],
     "vcf_dct_rdoq_tile": [],

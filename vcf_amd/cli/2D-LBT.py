@@ -12,4 +12,4 @@ from vcf_amd.codec.main import main  # noqa: E402
 from vcf_amd.codec.lbt2d import CoDec  # noqa: E402
 
 if __name__ == "__main__":
-    main(P.lbt_parser(entropy=P.entropy_of(sys.argv[1:])), CoDec)
+    main(P.lbt_parser(entropy=P.entropy_of(sys.argv[1:]), filter=P.filter_of(sys.argv[1:])), CoDec)

@@ -40,6 +40,7 @@ class BlockCoDec(EICCoDec):
     COLOR_REFUSAL = None                      # NotImplementedError texts, formatted with the refused name
     QUANTIZER_REFUSAL = None
     FILTER_CHECKED_ALWAYS = False             # else -f is checked when decoding only
+    DEBLOCK_REFUSAL = None                    # why -f deblock cannot run on this codec (MDCT), or None
     FLAG_MASK = ~0
     FRAME_ERROR = None                        # _check_frame's ValueError text
 
@@ -51,8 +52,11 @@ class BlockCoDec(EICCoDec):
             raise NotImplementedError(self.COLOR_REFUSAL.format(ct))
         self.lm = self._quantizer(args)
         filt = getattr(args, "filter", "no_filter")
-        if (self.FILTER_CHECKED_ALWAYS or not self.encoding) and filt != "no_filter":
-            raise NotImplementedError(f"filter {filt!r}: only no_filter is on the HIP path")
+        self.deblock = None                   # -f deblock when decoding: (beta, tc), None where a flag is absent
+        if filt == "deblock" and not self.encoding:
+            self.deblock = self._deblock_option(args)
+        elif (self.FILTER_CHECKED_ALWAYS or not self.encoding) and filt != "no_filter":
+            raise NotImplementedError(f"filter {filt!r}: only no_filter and deblock are on the HIP path")
         self.flags = _flags(args) & self.FLAG_MASK
         self._check_block_size()
         self.entropy = make_entropy(args)
@@ -67,6 +71,38 @@ class BlockCoDec(EICCoDec):
         if quant != "deadzone":
             raise NotImplementedError(self.QUANTIZER_REFUSAL.format(quant))
         return None
+
+    # ---- -f deblock (not in the reference; vcf_amd/deblock.py) ----
+    def _deblock_option(self, args):
+        from .. import deblock as DB
+        if self.DEBLOCK_REFUSAL is not None:
+            raise NotImplementedError(self.DEBLOCK_REFUSAL)
+        if self.block_size < DB.MIN_BLOCK_SIZE:
+            raise NotImplementedError(f"-f deblock with -B {self.block_size}: the filter reads three samples on each "
+                                      f"side of a block edge, so the blocks must be at least {DB.MIN_BLOCK_SIZE} wide")
+        beta, tc = getattr(args, "deblock_beta", None), getattr(args, "deblock_tc", None)
+        if (beta is not None and int(beta) < 0) or (tc is not None and int(tc) < 0):
+            raise ValueError(f"--deblock_beta {beta} / --deblock_tc {tc}: values >= 0")
+        return beta, tc
+
+    def _crop_offsets(self, H, W):
+        """(top, left): the rows and columns of padding this codec's decode crops."""
+        from .. import deblock as DB
+        return DB.crop_offsets(H, W, self.block_size)
+
+    def _post(self, QSS=None):
+        """None, or what follows the decode kernel on the device: post(d, n, H, W, stream=None) filters the
+        n decoded frames in d into a new buffer and returns (it, d), for round_trip to download the first
+        and free both."""
+        if self.deblock is None:
+            return None
+        from .. import deblock as DB
+        beta, tc = DB.strength(self.QSS if QSS is None else QSS, *self.deblock)
+
+        def post(d, n, H, W, stream=None, out=None):
+            top, left = self._crop_offsets(H, W)
+            return DB.deblock_device(d, n, H, W, self.block_size, top, left, beta, tc, out=out, stream=stream), d
+        return post
 
     # entropy stage (TIFF.py / CBAAC.py surface)
     def compress(self, img):

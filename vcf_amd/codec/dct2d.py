@@ -21,8 +21,8 @@ Lloyd-Max quantizer (histogram, design, encoder on the GPU,
 codec/quantizers.py) and decodes from its int16 output.  Options the HIP
 path does not implement raise NotImplementedError when the codec is
 constructed (block sizes above 4096, other colour transforms, quantizers
-other than deadzone and LloydMax, filters other than no_filter, -L with
-LloydMax); entropy codecs come from ENTROPY_CODECS.
+other than deadzone and LloydMax, filters other than no_filter and deblock
+(decode, B >= 4: vcf_amd/deblock.py), -L with LloydMax); entropy codecs come from ENTROPY_CODECS.
 """
 from __future__ import annotations
 
@@ -213,8 +213,11 @@ class CoDec(BlockCoDec):
         dk.free()
         rgb = D.raw_decode_device(y, 1, H, W, self.flags, block_size=self.block_size)
         y.free()
-        out = rgb.download(np.empty((H, W, 3), np.uint8))
-        rgb.free()
+        post = self._post()
+        bufs = (rgb,) if post is None else post(rgb, 1, H, W)
+        out = bufs[0].download(np.empty((H, W, 3), np.uint8))
+        for b in bufs:
+            b.free()
         return out
 
     def encode_indices(self, img: np.ndarray) -> np.ndarray:
@@ -231,7 +234,7 @@ class CoDec(BlockCoDec):
         self._deadzone_only("decode_indices")
         H, W = int(shape[0]), int(shape[1])
         return D.decode(np.ascontiguousarray(k, dtype=np.uint8), H, W, self.QSS, self.flags,
-                        self.block_size)
+                        self.block_size, post=self._post())
 
     def _encode_one(self, img):
         if self.lm is not None:
@@ -373,7 +376,7 @@ class CoDec(BlockCoDec):
         if all(isinstance(k, _Zipped) for k in items):
             return self._decode_zipped(items, shp)
         ks = [k.host() if isinstance(k, _Zipped) else k for k in items]
-        return D.decode(np.stack(ks), shp[0], shp[1], self.QSS, self.flags, self.block_size)
+        return D.decode(np.stack(ks), shp[0], shp[1], self.QSS, self.flags, self.block_size, post=self._post())
 
     def _decode_zipped(self, zs, shp):
         """n TIFFs of one shape -> n decoded frames: every strip inflated on the GPU
@@ -401,6 +404,15 @@ class CoDec(BlockCoDec):
         zlib_gpu.inflater().inflate_into(comp, comp_off, comp_len, dk, out_off, out_len, st)
         D.decode_device(dk, n, H, W, self.QSS, self.flags, out=drgb, stream=st, block_size=self.block_size)
         res = np.empty((n, H, W, 3), np.uint8)
-        drgb.download(res, st)
-        st.synchronize()
+        post = self._post()
+        if post is None:
+            drgb.download(res, st)
+            st.synchronize()
+            return res
+        dfil = post(drgb, n, H, W, stream=st)[0]      # -f deblock: one launch behind the decode, then the download
+        try:
+            dfil.download(res, st)
+            st.synchronize()
+        finally:
+            dfil.free()
         return res

@@ -83,6 +83,9 @@ class CoDec(EICCoDec):
         if quant != "deadzone":
             raise NotImplementedError(f"quantizer {quant!r}: only deadzone is on the HIP path")
         filt = getattr(args, "filter", "no_filter")
+        if not self.encoding and filt == "deblock":
+            raise NotImplementedError("filter 'deblock' with 2D-DWT: a wavelet transform of the whole frame has no "
+                                      "block edges (2D-DCT, 2D-KLT and 2D-LBT have them)")
         if not self.encoding and filt != "no_filter":
             raise NotImplementedError(f"filter {filt!r}: only no_filter is on the HIP path")
         self.entropy = make_entropy(args)

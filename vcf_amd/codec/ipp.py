@@ -90,6 +90,9 @@ class _IPP:
     """IPP_DCT.CoDec (:578-720) over a spatial codec base class (the MRO's next)."""
 
     def __init__(self, args, group=None):
+        if getattr(args, "filter", "no_filter") == "deblock":
+            raise NotImplementedError("filter 'deblock' with IPP: the filter would sit inside the prediction loop "
+                                      "and change the frames the encoder predicted from")
         super().__init__(args)
         if getattr(self, "lm", None) is not None:
             # the GOP loop keeps indices in HBM through the fused deadzone kernels

@@ -15,8 +15,9 @@ D x D eigenproblem runs on the host.  There is no CPU implementation of the
 hot path in the product.
 
 -B takes 2 <= B <= 16 (B = 1 and a frame of one block have no covariance
-matrix: ValueError, as in the reference).  -a deadzone, -t YCoCg and -f
-no_filter only; -p and -L are not options of this codec.
+matrix: ValueError, as in the reference).  -a deadzone and -t YCoCg only; -f
+no_filter, or deblock (decode, B >= 4: vcf_amd/deblock.py); -p and -L are not
+options of this codec.
 """
 from __future__ import annotations
 
@@ -46,6 +47,9 @@ class CoDec(BlockCoDec):
         if self.block_size > 16:
             raise NotImplementedError(f"block size {self.block_size}: the KLT kernels cover 2 <= B <= 16")
 
+    def _crop_offsets(self, H, W):
+        return K.padded_shape(H, W, self.block_size)[2:4]
+
     # ---- the hot path -------------------------------------------------------
     def _check_frame(self, img):
         super()._check_frame(img)
@@ -60,7 +64,7 @@ class CoDec(BlockCoDec):
     def decode_indices(self, k: np.ndarray, shape, weights32: np.ndarray) -> np.ndarray:
         """2D-KLT.py:738-809 on the GPU: u8 indices and the stored weights -> u8 RGB."""
         return K.decode(np.ascontiguousarray(k, dtype=np.uint8), int(shape[0]), int(shape[1]), self.QSS,
-                        self.flags, self.block_size, weights32)
+                        self.flags, self.block_size, weights32, post=self._post())
 
     def _encode_one(self, img):
         k, w64 = self.encode_indices(img)
@@ -105,4 +109,5 @@ class CoDec(BlockCoDec):
 
     def _decode_group(self, ks, shape, weights32):
         ks = np.stack([np.ascontiguousarray(k, dtype=np.uint8) for k in ks])
-        return K.decode(ks, shape[0], shape[1], self.QSS, self.flags, self.block_size, np.stack(weights32))
+        return K.decode(ks, shape[0], shape[1], self.QSS, self.flags, self.block_size, np.stack(weights32),
+                        post=self._post())

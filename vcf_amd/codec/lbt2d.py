@@ -16,7 +16,8 @@ implementation of the hot path in the product.
 
 The reference draws its initial weights unseeded; here they are seeded (see
 vcf_amd/lbt.py), so equal runs write equal files.  -B takes 2 <= B <= 8.
--a deadzone, -t YCoCg and -f no_filter only.  With --side_info every frame of
+-a deadzone and -t YCoCg only; -f no_filter, or deblock (decode, B >= 4:
+vcf_amd/deblock.py).  With --side_info every frame of
 a batch names the same file, as in the reference: it is for single frames.
 """
 from __future__ import annotations
@@ -61,6 +62,9 @@ class CoDec(BlockCoDec):
     def _check_block_size(self):
         L.check_block_size(self.block_size)
 
+    def _crop_offsets(self, H, W):
+        return L.padded_shape(H, W, self.block_size)[2:4]
+
     def _side_path(self, fn):
         return self.side_info if self.side_info is not None else f"{fn}.weights.pth"
 
@@ -77,7 +81,7 @@ class CoDec(BlockCoDec):
     def decode_indices(self, k: np.ndarray, shape, weights: np.ndarray, mean: float) -> np.ndarray:
         """2D-LBT.py:476-563 on the GPU: u8 indices, the stored matrix and mean -> u8 RGB."""
         return L.decode(np.ascontiguousarray(k, dtype=np.uint8), int(shape[0]), int(shape[1]), self.QSS,
-                        self.flags, self.block_size, weights, mean)
+                        self.flags, self.block_size, weights, mean, post=self._post())
 
     def _encode_one(self, img):
         k, wd, mean = self.encode_indices(img)
@@ -122,4 +126,5 @@ class CoDec(BlockCoDec):
     def _decode_group(self, ks, shape, extras):
         ks = np.stack([np.ascontiguousarray(k, dtype=np.uint8) for k in ks])
         return L.decode(ks, shape[0], shape[1], self.QSS, self.flags, self.block_size,
-                        np.stack([e[0] for e in extras]), np.array([e[1] for e in extras], np.float32))
+                        np.stack([e[0] for e in extras]), np.array([e[1] for e in extras], np.float32),
+                        post=self._post())

@@ -42,6 +42,8 @@ class CoDec(BlockCoDec):
     QUANTIZER_REFUSAL = ("quantizer {!r} with 2D-MDCT: only deadzone is on the HIP path "
                          "(LloydMax's B / 1.5 scale branch and uint16 indices are not built)")
     FRAME_ERROR = "Input image must be a 3D array."
+    DEBLOCK_REFUSAL = ("filter 'deblock' with 2D-MDCT: a lapped transform has no block edges "
+                       "(2D-DCT, 2D-KLT and 2D-LBT have them)")
 
     def __init__(self, args):
         super().__init__(args)

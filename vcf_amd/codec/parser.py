@@ -126,6 +126,28 @@ def add_deadzone(enc, dec):
                      help=f"Denoising filter (default: {DEFAULT_FILTER})", default=DEFAULT_FILTER)
 
 
+DEBLOCK = "deblock"                     # -f deblock: not in the reference (vcf_amd/deblock.py)
+
+
+def filter_of(argv) -> str:
+    """Pre-parse -f/--filter: the reference imports the module -f names, whose options then join the
+    parser (as -c CBAHC adds --order)."""
+    pre = argparse.ArgumentParser(add_help=False)
+    pre.add_argument("-f", "--filter", type=int_or_str, default=DEFAULT_FILTER)
+    return pre.parse_known_args(argv)[0].filter
+
+
+def add_deblock(dec):
+    """Not in the reference: the strengths of -f deblock (decode only; vcf_amd/deblock.py).  They join the
+    parser only when -f deblock was pre-parsed, so every other Namespace is the reference's."""
+    dec.add_argument("--deblock_beta", type=int, default=None, metavar="BETA",
+                     help="-f deblock: a line is filtered only where its second differences sum to less than "
+                          "BETA (default: -q, that is beta = Q)")
+    dec.add_argument("--deblock_tc", type=int, default=None, metavar="TC",
+                     help="-f deblock: the largest change of a sample beside a block edge "
+                          "(default: max(1, Q // 8) for -q Q)")
+
+
 def add_lloydmax(enc, dec):
     """LloydMax.py:27-35: -q as deadzone's, plus -m/--min_val and -n/--max_val (and -f on decode)."""
     add_deadzone(enc, dec)
@@ -262,15 +284,18 @@ def add_rdoq(enc):
 
 def dct_parser(description: str = "Exploiting spatial redundancy with the 2D Discrete Cosine "
                                   "Transform of constant block size.", quantizer: str = DEFAULT_QUANTIZER,
-               entropy: str = DEFAULT_EIC, rdoq: bool = False):
-    """The parser `python 2D-DCT.py ...` ends up with (the codec chain -a and -c name).  rdoq adds
-    --rdoq, as 2D-DCT.py does; without it the Namespace is the reference's."""
+               entropy: str = DEFAULT_EIC, rdoq: bool = False, filter: str = DEFAULT_FILTER):
+    """The parser `python 2D-DCT.py ...` ends up with (the codec chain -a, -c and -f name).  rdoq adds
+    --rdoq, as 2D-DCT.py does, and filter="deblock" --deblock_beta and --deblock_tc; without them
+    the Namespace is the reference's."""
     p, enc, dec = base_parser(description)
     add_dct(enc, dec)
     if rdoq:
         add_rdoq(enc)
     add_ycocg(enc, dec)
     add_quantizer(enc, dec, quantizer)
+    if filter == DEBLOCK:
+        add_deblock(dec)
     add_filter(enc, dec, entropy)
     add_eic(enc, dec)
     return p
@@ -289,25 +314,32 @@ def mdct_parser(description: str = "Exploiting spatial redundancy with the Modif
 
 
 def klt_parser(description: str = "Exploiting spatial redundancy with a learned block transform (the "
-                                  "Karhunen-Loeve transform of the image's blocks).", entropy: str = DEFAULT_EIC):
-    """`python 2D-KLT.py ...` (2D-KLT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py)."""
+                                  "Karhunen-Loeve transform of the image's blocks).", entropy: str = DEFAULT_EIC,
+               filter: str = DEFAULT_FILTER):
+    """`python 2D-KLT.py ...` (2D-KLT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py);
+    filter="deblock" adds --deblock_beta and --deblock_tc."""
     p, enc, dec = base_parser(description)
     add_klt(enc, dec)
     add_ycocg(enc, dec)
     add_deadzone(enc, dec)
+    if filter == DEBLOCK:
+        add_deblock(dec)
     add_filter(enc, dec, entropy)
     add_eic(enc, dec)
     return p
 
 
 def lbt_parser(description: str = "Exploiting spatial redundancy with the 2D Discrete Cosine Transform of "
-                                  "constant block size.", entropy: str = DEFAULT_EIC):
+                                  "constant block size.", entropy: str = DEFAULT_EIC,
+               filter: str = DEFAULT_FILTER):
     """`python 2D-LBT.py ...` (2D-LBT.py -> YCoCg.py -> deadzone.py -> no_filter.py -> TIFF.py); the
-    description is the reference's own docstring."""
+    description is the reference's own docstring.  filter="deblock" adds --deblock_beta and --deblock_tc."""
     p, enc, dec = base_parser(description)
     add_lbt(enc, dec)
     add_ycocg(enc, dec)
     add_deadzone(enc, dec)
+    if filter == DEBLOCK:
+        add_deblock(dec)
     add_filter(enc, dec, entropy)
     add_eic(enc, dec)
     return p
@@ -355,10 +387,10 @@ def rate_control_parser(description: str = "2D-DCT coding under a byte budget: -
 
 def iii_parser(description: str = "III coding: runs a 2D image codec for each image of a sequence.",
                transform: str = "2D-DCT", entropy: str = DEFAULT_EIC, rate_control: bool = False,
-               rdoq: bool = False):
+               rdoq: bool = False, filter: str = DEFAULT_FILTER):
     """`python III.py ...` (III.py + the chain of the 2D codec it imports).  rate_control adds
-    --target_bpp, --target_bytes and --q_from_files, rdoq adds --rdoq, as III.py does; without
-    them the Namespace is the reference's."""
+    --target_bpp, --target_bytes and --q_from_files, rdoq adds --rdoq, filter="deblock"
+    --deblock_beta and --deblock_tc, as III.py does; without them the Namespace is the reference's."""
     p, enc, dec = base_parser(description)
     add_iii(enc, dec)
     if rate_control:
@@ -377,6 +409,8 @@ def iii_parser(description: str = "III coding: runs a 2D image codec for each im
         add_dct(enc, dec)
     add_ycocg(enc, dec)
     add_deadzone(enc, dec)
+    if filter == DEBLOCK:
+        add_deblock(dec)
     add_filter(enc, dec, entropy)
     add_eic(enc, dec)
     return p
@@ -514,11 +548,17 @@ def rde_parser(description: str = "Compute the rate/distortion efficiency (J=R+D
 def rd_curve_parser(description: str = "Rate-distortion curve of the default chain (2D-DCT, YCoCg, deadzone, "
                                        "TIFF) with the frames resident on the GPU. This program has no "
                                        "counterpart in the reference: it replaces a loop of 2D-DCT.py encode, "
-                                       "2D-DCT.py decode and RDE.py over -q values.", rdoq: bool = False):
-    """`python RD-curve.py ...`: -B, -p and -x as 2D-DCT.py names them; rdoq adds --rdoq."""
+                                       "2D-DCT.py decode and RDE.py over -q values.", rdoq: bool = False,
+                    filter: str = DEFAULT_FILTER):
+    """`python RD-curve.py ...`: -B, -p and -x as 2D-DCT.py names them; rdoq adds --rdoq, filter="deblock"
+    -f, --deblock_beta and --deblock_tc."""
     p = argparse.ArgumentParser(description=description)
     if rdoq:
         add_rdoq(p)
+    if filter == DEBLOCK:
+        p.add_argument("-f", "--filter", type=int_or_str, default=DEFAULT_FILTER,
+                       help=f"Filter the reconstructions before they are measured: deblock (default: {DEFAULT_FILTER})")
+        add_deblock(p)
     p.add_argument("-o", "--original", type=str, default=ORIGINAL,
                    help="Input image; with -N a printf pattern of the frame number; or an .npy file holding "
                         "N x H x W x 3 uint8 frames (default: %(default)s)")

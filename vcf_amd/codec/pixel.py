@@ -27,6 +27,9 @@ class _PixelCoDec(EICCoDec):
     def __init__(self, args):
         super().__init__(args)
         filt = getattr(args, "filter", "no_filter")
+        if not self.encoding and filt == "deblock":
+            raise NotImplementedError("filter 'deblock': this codec has no block grid whose edges it could smooth "
+                                      "(2D-DCT, 2D-KLT and 2D-LBT have one)")
         if not self.encoding and filt != "no_filter":
             raise NotImplementedError(f"filter {filt!r}: only no_filter is on the HIP path")
         self.entropy = make_entropy(args)

@@ -254,7 +254,8 @@ def _hwc(a: np.ndarray):
     return a.shape if a.ndim == 3 else a.shape + (1,)
 
 
-def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False, rdoq=None) -> list:
+def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False, rdoq=None,
+             filter: str = "no_filter", deblock_beta=None, deblock_tc=None) -> list:
     """The rate-distortion curve of the default chain (2D-DCT.py: YCoCg, B x B DCT, deadzone, -c TIFF) over the
     quantization steps Qs, with the n equal-shape H x W x 3 u8 frames uploaded once.  Per Q, on the device:
     dct.encode_device, the deflate of the TIFF strips for their sizes (zlib_gpu.tiff_sizes_device), dct.decode_device
@@ -267,12 +268,19 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False
     the GPU deflate does not cover the frame (rows over 64 KB): the host TIFF writer's sizes would be the same, but a
     silent change of path is not this function's to make.  rdoq = MU codes the indices with the two-pass RDOQ
     pipeline (vcf_amd/rdoq.py, lambda = MU * Q * Q; B = 8 without -p only) instead of the plain encode: the same
-    curve, to be read against the plain one at equal Q or at equal bytes."""
+    curve, to be read against the plain one at equal Q or at equal bytes.  filter = "deblock" filters the
+    reconstructions on the device (vcf_amd/deblock.py: the strengths given, or deblock.default_strength(Q)) before
+    the distortion and SSIM kernels; the bytes are those of the unfiltered curve."""
     from .. import dct as D
+    from .. import deblock as DB
     from .. import rdoq as R
     from .. import zlib_gpu
     if rdoq is not None and (block_size != 8 or flags & D.VCF_DCT_PERCEPTUAL):
         raise NotImplementedError("--rdoq: the RDOQ encode has the 8x8 kernel without -p only")
+    if filter not in ("no_filter", "deblock"):
+        raise NotImplementedError(f"filter {filter!r}: only no_filter and deblock are on the HIP path")
+    if filter == "deblock" and block_size < DB.MIN_BLOCK_SIZE:
+        raise NotImplementedError(f"filter 'deblock' with -B {block_size}: blocks of at least {DB.MIN_BLOCK_SIZE}")
     f = np.asarray(frames)
     if f.dtype != np.uint8:
         raise TypeError(f"frames must be uint8, got {f.dtype}")
@@ -297,6 +305,10 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False
         k, rec = DeviceBuffer(n * Hp * Wp * 3), DeviceBuffer(n * H * W * 3)
         out = DeviceBuffer(n * 3 * DS.RECORD.itemsize)
         bufs += [src, k, rec, out]
+        if filter == "deblock":
+            fil = DeviceBuffer(n * H * W * 3)
+            bufs.append(fil)
+            top, left = DB.crop_offsets(H, W, block_size)
         if ssim:
             sout = DeviceBuffer(n * 3 * DS.SSIM_RECORD.itemsize)
             bufs.append(sout)
@@ -310,9 +322,13 @@ def rd_curve(frames, Qs, block_size: int = 8, flags: int = 0, ssim: bool = False
                 R.encode_frames_device(src, n, H, W, Q, R.lambda_of(rdoq, Q), flags, out=k)
             tif = zlib_gpu.tiff_sizes_device(k, n, (Hp, Wp, 3), np.uint8, stream=st)
             D.decode_device(k, n, H, W, Q, flags, out=rec, stream=st, block_size=block_size)
-            DS.sse_device(src, rec, n, H, W, 3, out, st)
+            dec = rec
+            if filter == "deblock":
+                beta, tc = DB.strength(Q, deblock_beta, deblock_tc)
+                dec = DB.deblock_device(rec, n, H, W, block_size, top, left, beta, tc, out=fil, stream=st)
+            DS.sse_device(src, dec, n, H, W, 3, out, st)
             if ssim:
-                DS.ssim_device(src, rec, n, H, W, 3, sout, st)
+                DS.ssim_device(src, dec, n, H, W, 3, sout, st)
             m = DS.records(out, n, 3, H * W, st)
             by = tif + 12
             bpp = by * 8 / (H * W)
@@ -361,19 +377,22 @@ def _curve_frames(original: str, n):
 
 
 def curve_main(argv=None) -> int:
-    """`python RD-curve.py -o ... -q 8,16,32 [-N n] [-B b] [-p] [-x] [--ssim] [--rdoq MU] [--json]`."""
+    """`python RD-curve.py -o ... -q 8,16,32 [-N n] [-B b] [-p] [-x] [--ssim] [--rdoq MU] [-f deblock
+    [--deblock_beta b] [--deblock_tc t]] [--json]`."""
     import json
     import sys
 
     from .. import dct as D
     from . import parser as P
-    args = P.rd_curve_parser(rdoq=True).parse_args(argv)
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = P.rd_curve_parser(rdoq=True, filter=P.filter_of(argv)).parse_args(argv)
     Qs = [int(q) for q in str(args.QSS).split(",") if q.strip()]
     frames = _curve_frames(args.original, args.number_of_frames)
     try:
         curve = rd_curve(frames, Qs, int(args.block_size_DCT),
                          D.flags_from(args.disable_subbands, args.perceptual_quantization), ssim=args.ssim,
-                         rdoq=args.rdoq)
+                         rdoq=args.rdoq, filter=getattr(args, "filter", "no_filter"),
+                         deblock_beta=getattr(args, "deblock_beta", None), deblock_tc=getattr(args, "deblock_tc", None))
     except DS.SsimShapeError as e:
         print(f"RD: {e}", file=sys.stderr)
         return 1

@@ -86,15 +86,18 @@ def encode(rgb: np.ndarray, Q: int = 32, flags: int = 0, block_size: int = 8,
 
 
 def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, block_size: int = 8,
-           variant: int = 0) -> np.ndarray:
-    """Host convenience: HpxWpx3 (or N...) u8 indices -> HxWx3 u8 reconstruction."""
+           variant: int = 0, post=None) -> np.ndarray:
+    """Host convenience: HpxWpx3 (or N...) u8 indices -> HxWx3 u8 reconstruction.  post(d, n, H, W) ->
+    (buffer to download, *buffers to free) runs on the decoded frames d before the download (-f deblock)."""
     f = _frames(k, "k")
     Hp, Wp = padded_shape(H, W, block_size)
     if f.shape[1:3] != (Hp, Wp):
         raise ValueError(f"index frames {f.shape[1:3]} do not match {(Hp, Wp)} for {H}x{W}")
-    return round_trip(f, np.asarray(k).ndim == 3,
-                      lambda din: decode_device(din, len(f), H, W, Q, flags, block_size=block_size, variant=variant),
-                      (H, W, 3))
+    def launch(din):
+        d = decode_device(din, len(f), H, W, Q, flags, block_size=block_size, variant=variant)
+        return d if post is None else post(d, len(f), H, W)
+
+    return round_trip(f, np.asarray(k).ndim == 3, launch, (H, W, 3))
 
 
 def _k32(name: str, nbytes: int, n: int, H: int, W: int, block_size: int, Q: int, flags: int):

@@ -166,9 +166,10 @@ def encode(frames: np.ndarray, Q: int = 32, flags: int = 0, B: int = 8, weights:
 
 
 def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, B: int = 8,
-           weights32: np.ndarray | None = None) -> np.ndarray:
+           weights32: np.ndarray | None = None, post=None) -> np.ndarray:
     """Host convenience: HpxWpx3 (or N...) u8 indices and the float32 weights of
-    {out}_weights.npz -> HxWx3 u8 reconstruction."""
+    {out}_weights.npz -> HxWx3 u8 reconstruction.  post(d, n, H, W) -> (buffer to download, *buffers to
+    free) runs on the decoded frames d before the download (-f deblock)."""
     if weights32 is None:
         raise ValueError("decode needs the float32 weights the encoder stored")
     f = frames_u8(k, "k")
@@ -177,6 +178,8 @@ def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, B: int = 
     Hp, Wp = padded_shape(H, W, B)[:2]
     if f.shape[1:3] != (Hp, Wp):
         raise ValueError(f"index frames {f.shape[1:3]} do not match {(Hp, Wp)} for {H}x{W}")
-    return round_trip(f, np.asarray(k).ndim == 3,
-                      lambda din, dw: decode_device(din, n, H, W, dw, Q, flags, block_size=B), (H, W, 3),
-                      extra=[_weights(weights32, n, B, np.float32)])
+    def launch(din, dw):
+        d = decode_device(din, n, H, W, dw, Q, flags, block_size=B)
+        return d if post is None else post(d, n, H, W)
+
+    return round_trip(f, np.asarray(k).ndim == 3, launch, (H, W, 3), extra=[_weights(weights32, n, B, np.float32)])

@@ -249,9 +249,11 @@ def encode(frames: np.ndarray, Q: int = 32, flags: int = 0, B: int = 8, weights=
     return (res, side["w"][0], side["m"][0]) if single else (res, side["w"], side["m"])
 
 
-def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, B: int = 8, weights=None, mean=None):
+def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, B: int = 8, weights=None, mean=None,
+           post=None):
     """Host convenience: HpxWpx3 (or N...) u8 indices, the float32 decoder matrix and the mean of
-    {out}.weights.pth -> HxWx3 u8 reconstruction."""
+    {out}.weights.pth -> HxWx3 u8 reconstruction.  post(d, n, H, W) -> (buffer to download, *buffers to
+    free) runs on the decoded frames d before the download (-f deblock)."""
     check_block_size(B)
     if weights is None or mean is None:
         raise ValueError("decode needs the decoder matrix and the mean the encoder stored")
@@ -260,6 +262,9 @@ def decode(k: np.ndarray, H: int, W: int, Q: int = 32, flags: int = 0, B: int = 
     Hp, Wp = padded_shape(H, W, B)[:2]
     if f.shape[1:3] != (Hp, Wp):
         raise ValueError(f"index frames {f.shape[1:3]} do not match {(Hp, Wp)} for {H}x{W}")
-    return round_trip(f, np.asarray(k).ndim == 3,
-                      lambda din, dw, dm: decode_device(din, n, H, W, dw, dm, Q, flags, block_size=B), (H, W, 3),
+    def launch(din, dw, dm):
+        d = decode_device(din, n, H, W, dw, dm, Q, flags, block_size=B)
+        return d if post is None else post(d, n, H, W)
+
+    return round_trip(f, np.asarray(k).ndim == 3, launch, (H, W, 3),
                       extra=[_per_frame(weights, n, B * B, "decoder weights"), _means(mean, n)])
