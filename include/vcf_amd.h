@@ -451,6 +451,48 @@ int vcf_ipp_block_match(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, 
 int vcf_ipp_motion_compensate(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,
                               uint8_t *out_rgb_dev, void *stream);
 
+/* Sub-pel motion (--subpel; not in the reference).  Integers throughout.
+ * Vectors are in quarter-pel units q = (qx, qy), stored as float32 q / 4
+ * (exact).  A block at (i, j) of side bs reads the reference from
+ * X = 4 j + qx: ix = X >> 2 (arithmetic shift: floor), fx = X & 3; iy, fy the
+ * same from 4 i + qy.  Prediction sample (luma and each RGB channel alike),
+ * with a = r[y, x], b = r[y, x+1], c = r[y+1, x], d = r[y+1, x+1]:
+ *   p = ((4-fx)(4-fy) a + fx (4-fy) b + (4-fx) fy c + fx fy d + 8) >> 4;
+ * a tap whose weight is 0 is not read, fx = fy = 0 is the plain copy.  A
+ * vector is valid iff every sample it reads lies in the frame: ix >= 0,
+ * ix + bs + (fx ? 1 : 0) <= W, and the same for y with H.
+ * Search for precision N = subpel in {1, 2, 4}: stage 0 is
+ * vcf_ipp_block_match's integer search (same kernels, same tie rule); its
+ * vector times 4 is the centre.  N >= 2: a stage with step = 2 scans the 8
+ * neighbours centre + (ddx, ddy), ddx, ddy in {-step, 0, +step}, ddy outer
+ * and ddx inner; invalid neighbours are skipped; a neighbour's SAD is the
+ * interpolated reference luma (the u8 luma of the gray pass, interpolated)
+ * against the current luma; the winner is the argmin of (SAD, index) with the
+ * centre at index 0 and the neighbours 1..8 in scan order.  N = 4: a second
+ * stage with step = 1 around the first stage's winner.  N = 1 writes exactly
+ * what vcf_ipp_block_match writes.
+ * Kernel: one wave per block after the integer search, the block and the
+ * (bs + 2)^2 luma window around the integer winner in LDS, both stages in the
+ * one launch.  Limits and alignment as vcf_ipp_block_match: bs <= 64,
+ * sr <= 32, mv_dev 4-byte aligned, the frames and the workspace unaligned;
+ * a violation, or subpel outside {1, 2, 4}, is VCF_ERR_INVALID before any
+ * device work.  Written: the (H/bs) * (W/bs) * 2 floats at mv_dev and the
+ * 2*H*W workspace bytes. */
+int vcf_ipp_block_match_subpel(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, int32_t bs,
+                               int32_t sr, int32_t fast, int32_t subpel, float *mv_dev, uint8_t *gray_workspace_dev,
+                               void *stream);
+
+/* Compensation of an arbitrary float field under the rule above:
+ * q = lrintf(4 m) per component; an invalid vector falls back to the
+ * co-located block, pixels outside the full-block area are 0 (both as
+ * vcf_ipp_motion_compensate); for integer-valued fields the output equals
+ * vcf_ipp_motion_compensate's bit for bit.  The frames need no alignment (a
+ * 4-byte aligned reference is read in words, an aligned output written in
+ * words); mv_dev must be 4-byte aligned (VCF_ERR_INVALID before any device
+ * work); H <= 65535.  Writes the H * W * 3 bytes at out_rgb_dev. */
+int vcf_ipp_motion_compensate_qpel(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,
+                                   uint8_t *out_rgb_dev, void *stream);
+
 /* residual_shifted = clip(cur - comp + 128, 0, 255) (IPP_DCT.py:547-551).  No
  * pointer needs alignment; writes the n bytes at out_dev. */
 int vcf_ipp_residual(const uint8_t *cur_dev, const uint8_t *comp_dev, int64_t n, uint8_t *out_dev, void *stream);

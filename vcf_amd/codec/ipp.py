@@ -25,6 +25,9 @@ mixed-mode frame :489-505 and its reconstruction :512-526); the motion file
 then also carries each P frame's mode map, like the reference's
 {"mv", "modes"} entries, and the decoder reconstructs mode by mode
 (:770-790).
+--subpel 2 / 4 (not in the reference) refines the vectors to half / quarter
+pel and predicts by bilinear interpolation (vcf_amd/csrc/vcf_ipp_subpel.hip);
+meta.json then carries "subpel" and the decoder interpolates alike.
 """
 from __future__ import annotations
 
@@ -104,6 +107,10 @@ class _IPP:
             self.search_range = 8
         self.use_fast = bool(getattr(args, "fast", False))
         self.rdo_lambda = float(getattr(args, "rdo_lambda", 0.0) or 0.0)
+        # motion precision (not in the reference): 1 whole, 2 half, 4 quarter pel; the decoder takes it from meta.json
+        self.subpel = int(getattr(args, "subpel", 1) or 1)
+        if self.subpel not in (1, 2, 4):
+            raise ValueError(f"--subpel {self.subpel}: 1, 2 or 4")
         self.prefix = resolve_prefix(args.output) if getattr(args, "output", None) else None
         self.group = group if group is not None else shard.Group()
 
@@ -125,8 +132,12 @@ class _IPP:
         ref = recon_I
         for p in range(1, min(self.gop_size, len(frames) - g0)):
             cur = frames[g0 + p]
-            mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast)
-            comp = K.motion_compensate(ref, mv, bs)
+            if self.subpel > 1:
+                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, subpel=self.subpel)
+                comp = K.motion_compensate(ref, mv, bs, subpel=self.subpel)
+            else:
+                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast)
+                comp = K.motion_compensate(ref, mv, bs)
             if self.rdo_lambda > 0:
                 # :441-536: per-block I/P decision, the mixed-mode frame, its reconstruction
                 modes = K.rdo_modes(cur, comp, bs, self.QSS, self.rdo_lambda)
@@ -204,6 +215,8 @@ class _IPP:
         meta = {"n_frames": self.N_frames, "width": self.width, "height": self.height, "gop_size": self.gop_size,
                 "total_bits": total_bits, "I_info": I_infos, "P_info": P_infos,
                 "mv_file": f"{os.path.basename(self.prefix)}_mv.npz", "base_prefix": os.path.basename(self.prefix)}
+        if self.subpel > 1:
+            meta["subpel"] = self.subpel   # fractional vectors: the decoder must interpolate
         with open(f"{self.prefix}_meta.json", "w") as f:
             json.dump(meta, f, indent=4)
         return total_bits
@@ -227,6 +240,7 @@ class _IPP:
         _ensure_dir(out_prefix)
         gop, N = meta["gop_size"], meta["n_frames"]
         bs = self.block_size_ME
+        subpel = int(meta.get("subpel", 1))
         recon, p_idx = [], 0
         for i_idx, g0 in enumerate(range(0, N, gop)):
             if i_idx >= len(meta["I_info"]):
@@ -235,7 +249,8 @@ class _IPP:
             recon.append(ref)
             for p in range(1, min(gop, N - g0)):
                 rec_res = self._decode_frame(f"{in_prefix}_P_{p_idx}_enc")
-                pred = K.motion_compensate(ref, mvs[p_idx], bs)
+                pred = K.motion_compensate(ref, mvs[p_idx], bs, subpel=subpel) if subpel > 1 else \
+                    K.motion_compensate(ref, mvs[p_idx], bs)
                 if modes is not None:   # RDO was used: mode-aware reconstruction (:770-790)
                     ref = K.rdo_reconstruct(pred, rec_res, modes[p_idx], bs)
                 else:
@@ -321,9 +336,14 @@ class CoDec(_IPP, DCTCoDec):
                 futs = []
                 for p in range(1, min(self.gop_size, len(frames) - g0)):
                     upload(frames[g0 + p])
-                    call("vcf_ipp_block_match", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
-                         int(bool(self.use_fast)), dmv.ptr, dgray.ptr, sh)
-                    call("vcf_ipp_motion_compensate", ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
+                    if self.subpel > 1:
+                        call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
+                             int(bool(self.use_fast)), self.subpel, dmv.ptr, dgray.ptr, sh)
+                        call("vcf_ipp_motion_compensate_qpel", ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
+                    else:
+                        call("vcf_ipp_block_match", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
+                             int(bool(self.use_fast)), dmv.ptr, dgray.ptr, sh)
+                        call("vcf_ipp_motion_compensate", ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
                     mv = np.zeros((hb, wb, 2), np.float32)
                     if mv.size:
                         call("vcf_memcpy_dtoh", mv.ctypes.data_as(ctypes.c_void_p), dmv.ptr, mv.nbytes, sh)

@@ -51,10 +51,13 @@ class DeviceIPP:
     deadzone Q, the reference's default -c TIFF), full search or --fast."""
 
     def __init__(self, comm, rank: int, world: int, n_frames: int, H: int, W: int, Q: int = 32, gop: int = 10,
-                 bs: int = 16, sr: int = 8, fast: bool = False):
+                 bs: int = 16, sr: int = 8, fast: bool = False, subpel: int = 1):
         self.comm, self.rank, self.world = comm, int(rank), int(world)
         self.N, self.H, self.W, self.Q = int(n_frames), int(H), int(W), int(Q)
         self.gop, self.bs, self.sr, self.fast = int(gop), int(bs), int(sr), bool(fast)
+        if subpel not in (1, 2, 4):
+            raise ValueError(f"subpel {subpel!r}: 1, 2 or 4")
+        self.subpel = int(subpel)   # > 1: half / quarter-pel vectors and the bilinear compensator
         self.n_gops = (self.N + self.gop - 1) // self.gop
         self.g_lo, self.g_hi = frame_range(self.n_gops, self.rank, self.world)
 
@@ -127,9 +130,14 @@ class DeviceIPP:
                     continue
                 ref, comp = _At(self.ref, g * fb, fb), _At(self.comp, g * fb, fb)
                 mv = _At(self.mv, f * self.mvb, self.mvb)
-                call("vcf_ipp_block_match", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr, int(self.fast),
-                     mv.ptr, self.gray.ptr, sh)
-                call("vcf_ipp_motion_compensate", ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
+                if self.subpel > 1:
+                    call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr,
+                         int(self.fast), self.subpel, mv.ptr, self.gray.ptr, sh)
+                    call("vcf_ipp_motion_compensate_qpel", ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
+                else:
+                    call("vcf_ipp_block_match", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr, int(self.fast),
+                         mv.ptr, self.gray.ptr, sh)
+                    call("vcf_ipp_motion_compensate", ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
                 call("vcf_ipp_residual", cur.ptr, comp.ptr, fb, self.res.address(j * fb), sh)
                 p_frames.append(f)
             n = len(gs)

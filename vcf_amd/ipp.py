@@ -17,12 +17,23 @@ def _rgb(a):
     return a
 
 
+def _check_subpel(subpel) -> int:
+    if subpel not in (1, 2, 4):
+        raise ValueError(f"subpel {subpel!r}: 1 (whole), 2 (half) or 4 (quarter pel)")
+    return int(subpel)
+
+
 def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, fast: bool = False,
-                   variant: int = 0) -> np.ndarray:
+                   variant: int = 0, subpel: int = 1) -> np.ndarray:
     """IPP.block_matching (IPP_DCT.py:344-376) -> (H//bs, W//bs, 2) float32 (dx, dy).
     variant 0: word kernels (full search for bs % 4 == 0, parallel-round TSS for bs 16; the product's rule),
-    1: byte / serial kernels (the A/B library's twin; same vectors)."""
+    1: byte / serial kernels (the A/B library's twin; same vectors).
+    subpel 2 / 4: the integer search refined to half / quarter pel (vcf_ipp_block_match_subpel;
+    not in the reference), vectors in multiples of 1/subpel."""
     ref, cur = _rgb(ref), _rgb(cur)
+    subpel = _check_subpel(subpel)
+    if subpel > 1 and variant != 0:
+        raise ValueError("the sub-pel search runs after the product's integer kernels (variant 0)")
     H, W = ref.shape[:2]
     mv = np.zeros((H // bs, W // bs, 2), np.float32)
     if mv.size == 0:
@@ -30,16 +41,23 @@ def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, 
     dr, dc = DeviceBuffer.from_array(ref), DeviceBuffer.from_array(cur)
     dm, dg = DeviceBuffer(mv.nbytes), DeviceBuffer(2 * H * W)
     try:
-        L.call_v(int(variant), "vcf_ipp_block_match", dr.ptr, dc.ptr, H, W, int(bs), int(sr), int(bool(fast)), dm.ptr,
-                 dg.ptr, None)
+        if subpel > 1:
+            L.call("vcf_ipp_block_match_subpel", dr.ptr, dc.ptr, H, W, int(bs), int(sr), int(bool(fast)), subpel,
+                   dm.ptr, dg.ptr, None)
+        else:
+            L.call_v(int(variant), "vcf_ipp_block_match", dr.ptr, dc.ptr, H, W, int(bs), int(sr), int(bool(fast)),
+                     dm.ptr, dg.ptr, None)
         return dm.download(mv)
     finally:
         for b in (dr, dc, dm, dg):
             b.free()
 
 
-def motion_compensate(frame: np.ndarray, mv: np.ndarray, bs: int = 16) -> np.ndarray:
+def motion_compensate(frame: np.ndarray, mv: np.ndarray, bs: int = 16, subpel: int = 1) -> np.ndarray:
+    """IPP.motion_compensate (IPP_DCT.py:378-395); subpel > 1: the bilinear quarter-pel
+    compensator (vcf_ipp_motion_compensate_qpel), which rounds the field to quarter pels."""
     frame = _rgb(frame)
+    name = "vcf_ipp_motion_compensate_qpel" if _check_subpel(subpel) > 1 else "vcf_ipp_motion_compensate"
     H, W = frame.shape[:2]
     mv = np.ascontiguousarray(mv, np.float32)
     if mv.shape != (H // bs, W // bs, 2):
@@ -48,7 +66,7 @@ def motion_compensate(frame: np.ndarray, mv: np.ndarray, bs: int = 16) -> np.nda
     df, dm, do = DeviceBuffer.from_array(frame), DeviceBuffer.from_array(mv if mv.size else np.zeros(2, np.float32)), \
         DeviceBuffer(frame.nbytes)
     try:
-        L.call("vcf_ipp_motion_compensate", df.ptr, dm.ptr, H, W, int(bs), do.ptr, None)
+        L.call(name, df.ptr, dm.ptr, H, W, int(bs), do.ptr, None)
         return do.download(out)
     finally:
         for b in (df, dm, do):
