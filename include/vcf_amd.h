@@ -527,6 +527,35 @@ int vcf_ipp_rdo_residual(const uint8_t *cur_dev, const uint8_t *comp_dev, const 
 int vcf_ipp_rdo_reconstruct(const uint8_t *comp_dev, const uint8_t *rec_dev, const uint8_t *modes_dev, int32_t H,
                             int32_t W, int32_t bs, uint8_t *out_dev, void *stream);
 
+/* B-frames (--bframes; not in the reference).  Integers throughout.  cur is the
+ * frame to code, cf and cb the compensations of the past and of the future
+ * anchor's reconstruction (H x W x 3 u8 each, as the compensators write them:
+ * 0 outside the full-block area).  Candidates per byte: p0 = cf, p1 = cb,
+ * p2 = (cf + cb + 1) >> 1.  For every full bs x bs block SAD_m is the sum of
+ * |cur - p_m| over the block's bs * bs * 3 bytes and the block's mode is the
+ * argmin of (SAD_m, m): ties go to the lower m.  pred is the winner inside
+ * each full block and 0 outside the full-block area.
+ * vcf_ipp_bipred_residual writes the (H/bs) x (W/bs) mode bytes at modes_dev
+ * and clip(cur - pred + 128, 0, 255) over all H * W * 3 bytes at res_dev, in
+ * one launch that reads each source once; pred itself is never written.
+ * Limits: 1 <= bs <= 64, H <= 65535, H * W * 3 < 2^31; a violation or a null
+ * frame is VCF_ERR_INVALID before any device work.  No pointer needs
+ * alignment (4-byte aligned frames with W * 3 a multiple of 4 are read and
+ * written in words).  An empty field (H < bs or W < bs) is legal: modes_dev
+ * may be NULL, nothing is written there, and the residual follows from
+ * pred = 0.  Written: (H/bs) * (W/bs) bytes at modes_dev and H * W * 3 bytes at
+ * res_dev. */
+int vcf_ipp_bipred_residual(const uint8_t *cur_dev, const uint8_t *cf_dev, const uint8_t *cb_dev, int32_t H, int32_t W,
+                            int32_t bs, uint8_t *modes_dev, uint8_t *res_dev, void *stream);
+
+/* The decoder's side of the rule above: pred rebuilt from cf, cb and the mode
+ * map, then clip(pred + rec - 128, 0, 255) over all H * W * 3 bytes.  A mode
+ * byte above 2 is the caller's error and behaves as mode 0.  Limits, alignment
+ * and the empty field as vcf_ipp_bipred_residual (modes_dev is only read).
+ * Written: H * W * 3 bytes at out_dev. */
+int vcf_ipp_bipred_reconstruct(const uint8_t *cf_dev, const uint8_t *cb_dev, const uint8_t *modes_dev,
+                               const uint8_t *rec_dev, int32_t H, int32_t W, int32_t bs, uint8_t *out_dev, void *stream);
+
 /* ---- CBAAC entropy codec (CBAAC.py), host code --------------------------------- */
 
 /* Worst-case code-stream bytes for n symbols. */

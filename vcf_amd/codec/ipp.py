@@ -28,6 +28,13 @@ then also carries each P frame's mode map, like the reference's
 --subpel 2 / 4 (not in the reference) refines the vectors to half / quarter
 pel and predicts by bilinear interpolation (vcf_amd/csrc/vcf_ipp_subpel.hip);
 meta.json then carries "subpel" and the decoder interpolates alike.
+--bframes N (not in the reference) puts N bidirectionally predicted frames
+between two anchors (gop_types): an anchor predicts from the anchor before it,
+a B-frame from both anchors around it, block by block from the past one, the
+future one or their average (vcf_amd/csrc/vcf_ipp_bipred.hip), and nothing
+predicts from a B-frame.  The B-frames go to {prefix}_B_{n}_enc files, their
+fields and mode maps to "bmv_f32" / "bmodes_u8" of the motion file, and
+meta.json carries "bframes", "frame_types" and "B_info".
 """
 from __future__ import annotations
 
@@ -89,6 +96,33 @@ def read_frames(src: str, n: int):
     return [read_image(f)[0] for f in files]
 
 
+MAX_BFRAMES = 7
+
+
+def gop_types(L: int, N: int) -> str:
+    """Display-order frame types of a GOP of L frames with N B-frames between two anchors:
+    I first, anchors every N + 1 frames and at the last frame, B strictly between anchors."""
+    if L < 1 or not 0 <= N <= MAX_BFRAMES:
+        raise ValueError(f"gop_types({L}, {N}): L >= 1 and 0 <= N <= {MAX_BFRAMES}")
+    t, a = ["B"] * L, 0
+    t[0] = "I"
+    while a < L - 1:
+        a = min(a + N + 1, L - 1)
+        t[a] = "P"
+    return "".join(t)
+
+
+def sequence_types(n_frames: int, gop_size: int, N: int) -> str:
+    """gop_types of every GOP of the sequence, in display order."""
+    return "".join(gop_types(min(gop_size, n_frames - g0), N) for g0 in range(0, n_frames, gop_size))
+
+
+def _anchor_intervals(types: str):
+    """(past anchor, closing anchor) positions of a GOP, in coding order."""
+    anchors = [i for i, t in enumerate(types) if t != "B"]
+    return list(zip(anchors, anchors[1:]))
+
+
 class _IPP:
     """IPP_DCT.CoDec (:578-720) over a spatial codec base class (the MRO's next)."""
 
@@ -111,6 +145,12 @@ class _IPP:
         self.subpel = int(getattr(args, "subpel", 1) or 1)
         if self.subpel not in (1, 2, 4):
             raise ValueError(f"--subpel {self.subpel}: 1, 2 or 4")
+        # B-frames between two anchors (not in the reference); the decoder takes the structure from meta.json
+        self.bframes = int(getattr(args, "bframes", 0) or 0)
+        if not 0 <= self.bframes <= MAX_BFRAMES:
+            raise ValueError(f"--bframes {self.bframes}: 0 .. {MAX_BFRAMES}")
+        if self.bframes and self.rdo_lambda > 0:
+            raise NotImplementedError("--bframes with -R: no mode-decision anchors beside B-frames yet")
         self.prefix = resolve_prefix(args.output) if getattr(args, "output", None) else None
         self.group = group if group is not None else shard.Group()
 
@@ -125,6 +165,8 @@ class _IPP:
 
     def _gop(self, frames, g0, i_idx, p0):
         """One GOP: I-frame then P-frames (IPP.temporal_filter :397-575)."""
+        if self.bframes:
+            return self._gop_bframes(frames, g0, i_idx, p0)
         bs = self.block_size_ME
         recon_I, bits_I = self.encode_decode_proxy(frames[g0], "I", i_idx)
         I = {"bits": bits_I, "idx": g0}
@@ -157,6 +199,43 @@ class _IPP:
             recon.append(ref)
         return I, P, mvs, recon
 
+    def _b0(self, g0):
+        """The first B file index of the GOP at g0: every GOP before it is full."""
+        return (g0 // self.gop_size) * gop_types(self.gop_size, self.bframes).count("B")
+
+    def _gop_bframes(self, frames, g0, i_idx, p0):
+        """One GOP with B-frames: I, then per anchor interval the closing anchor (predicted from the
+        anchor before it) and the B-frames between in display order (predicted from both)."""
+        bs, sr, fast = self.block_size_ME, self.search_range, self.use_fast
+        kw = {"subpel": self.subpel} if self.subpel > 1 else {}
+        types = gop_types(min(self.gop_size, len(frames) - g0), self.bframes)
+        n_b = self._b0(g0)
+        recon_I, bits_I = self.encode_decode_proxy(frames[g0], "I", i_idx)
+        I = {"bits": bits_I, "idx": g0}
+        P, mvs, recon = [], [], {0: recon_I}
+        B = {"info": [], "mv": [], "modes": []}
+        for a, c in _anchor_intervals(types):
+            cur = frames[g0 + c]
+            mv = K.block_matching(recon[a], cur, bs, sr, fast, **kw)
+            comp = K.motion_compensate(recon[a], mv, bs, **kw)
+            rec_res, bits_P = self.encode_decode_proxy(K.residual(cur, comp), "P", p0 + len(P))
+            recon[c] = K.reconstruct(comp, rec_res)
+            mvs.append(mv)
+            P.append({"bits": bits_P})
+            for d in range(a + 1, c):
+                cur = frames[g0 + d]
+                mv_f = K.block_matching(recon[a], cur, bs, sr, fast, **kw)
+                mv_b = K.block_matching(recon[c], cur, bs, sr, fast, **kw)
+                cf = K.motion_compensate(recon[a], mv_f, bs, **kw)
+                cb = K.motion_compensate(recon[c], mv_b, bs, **kw)
+                modes, res = K.bipred_residual(cur, cf, cb, bs)
+                _, bits_B = self.encode_decode_proxy(res, "B", n_b)   # nothing predicts from a B-frame
+                n_b += 1
+                B["info"].append({"bits": bits_B})
+                B["mv"].append(np.stack([mv_f, mv_b]))
+                B["modes"].append(modes)
+        return I, P, mvs, [recon[i] for i in sorted(recon)], B
+
     def encode(self):
         g = self.group
         frames = read_frames(str(self.args.input), int(self.args.number_of_frames))
@@ -175,25 +254,31 @@ class _IPP:
             local = []
             for gi in range(lo, hi):
                 g0 = gi * self.gop_size
-                local.append(self._gop(frames, g0, gi, gi * (self.gop_size - 1)))
+                # the P files before this GOP: every GOP before it is full
+                local.append(self._gop(frames, g0, gi, gi * gop_types(self.gop_size, self.bframes).count("P")))
             for f in pending:
                 f.result()
         # gather per-GOP results on rank 0 (sizes as JSON, motion fields as bytes)
-        blob = json.dumps([[I, P] for I, P, _, _ in local]).encode()
+        nb = self.bframes
+        blob = json.dumps([[r[0], r[1]] + ([r[4]["info"]] if nb else []) for r in local]).encode()
         rdo = self.rdo_lambda > 0
         mv_of = (lambda m: m["mv"]) if rdo else (lambda m: m)
-        mvbytes = b"".join(mv_of(m).astype(np.float32).tobytes() for _, _, mvs, _ in local for m in mvs)
+        mvbytes = b"".join(mv_of(m).astype(np.float32).tobytes() for r in local for m in r[2])
         infos = self._gather(blob)
         mvs_all = self._gather(mvbytes)
         if rdo:
-            modes_all = self._gather(b"".join(m["modes"].tobytes() for _, _, mvs, _ in local for m in mvs))
+            modes_all = self._gather(b"".join(m["modes"].tobytes() for r in local for m in r[2]))
+        if nb:
+            bmv_all = self._gather(b"".join(m.astype(np.float32).tobytes() for r in local for m in r[4]["mv"]))
+            bmodes_all = self._gather(b"".join(m.astype(np.uint8).tobytes() for r in local for m in r[4]["modes"]))
         if g.rank != 0:
             return None
-        I_infos, P_infos = [], []
+        I_infos, P_infos, B_infos = [], [], []
         for b in infos:
-            for I, P in json.loads(b):
+            for I, P, *rest in json.loads(b):
                 I_infos.append(I)
                 P_infos.extend(P)
+                B_infos.extend(rest[0] if rest else [])
         hb, wb = self.height // self.block_size_ME, self.width // self.block_size_ME
         mv = np.frombuffer(b"".join(mvs_all), np.float32).reshape(len(P_infos), hb, wb, 2)
         mv_path = f"{self.prefix}_mv.npz"
@@ -208,8 +293,13 @@ class _IPP:
             obj = np.empty(len(P_infos), dtype=object)
             for i in range(len(P_infos)):
                 obj[i] = mv[i]
-            np.savez_compressed(mv_path, mv=np.array(list(obj), dtype=object), mv_f32=mv)
+            extra = {}
+            if nb:
+                extra["bmv_f32"] = np.frombuffer(b"".join(bmv_all), np.float32).reshape(len(B_infos), 2, hb, wb, 2)
+                extra["bmodes_u8"] = np.frombuffer(b"".join(bmodes_all), np.uint8).reshape(len(B_infos), hb, wb)
+            np.savez_compressed(mv_path, mv=np.array(list(obj), dtype=object), mv_f32=mv, **extra)
         total_bits = sum(i["bits"] for i in I_infos) + sum(p["bits"] for p in P_infos)
+        total_bits += sum(b["bits"] for b in B_infos)
         total_bits += os.path.getsize(mv_path) * 8
         self.total_bits = total_bits
         meta = {"n_frames": self.N_frames, "width": self.width, "height": self.height, "gop_size": self.gop_size,
@@ -217,6 +307,10 @@ class _IPP:
                 "mv_file": f"{os.path.basename(self.prefix)}_mv.npz", "base_prefix": os.path.basename(self.prefix)}
         if self.subpel > 1:
             meta["subpel"] = self.subpel   # fractional vectors: the decoder must interpolate
+        if nb:
+            meta["bframes"] = nb
+            meta["frame_types"] = sequence_types(self.N_frames, self.gop_size, nb)
+            meta["B_info"] = B_infos
         with open(f"{self.prefix}_meta.json", "w") as f:
             json.dump(meta, f, indent=4)
         return total_bits
@@ -236,11 +330,16 @@ class _IPP:
                                           "(written by the reference); re-encode or convert to 'mv_f32'")
             mvs = z["mv_f32"]
             modes = z["modes_u8"] if "modes_u8" in z.files else None
+            bmv = z["bmv_f32"] if "bmv_f32" in z.files else None
+            bmodes = z["bmodes_u8"] if "bmodes_u8" in z.files else None
         out_prefix = resolve_prefix(self.args.output)
         _ensure_dir(out_prefix)
         gop, N = meta["gop_size"], meta["n_frames"]
         bs = self.block_size_ME
         subpel = int(meta.get("subpel", 1))
+        if "bframes" in meta:
+            recon = self._decode_bframes(meta, in_prefix, mvs, bmv, bmodes, subpel)
+            return self._write_decoded(out_prefix, recon)
         recon, p_idx = [], 0
         for i_idx, g0 in enumerate(range(0, N, gop)):
             if i_idx >= len(meta["I_info"]):
@@ -257,6 +356,43 @@ class _IPP:
                     ref = K.reconstruct(pred, rec_res)
                 recon.append(ref)
                 p_idx += 1
+        return self._write_decoded(out_prefix, recon)
+
+    def _decode_bframes(self, meta, in_prefix, mvs, bmv, bmodes, subpel):
+        """The frames of a --bframes stream in display order: per GOP the I-frame, then per anchor
+        interval the closing anchor and the B-frames between."""
+        gop, N, nb = meta["gop_size"], meta["n_frames"], meta["bframes"]
+        if not (isinstance(nb, int) and 1 <= nb <= MAX_BFRAMES and isinstance(gop, int) and gop >= 1):
+            raise ValueError(f"meta.json: bframes {nb!r}, gop_size {gop!r}")
+        types = meta.get("frame_types")
+        if types != sequence_types(N, gop, nb):
+            raise ValueError(f"meta.json: frame_types {types!r} does not follow from n_frames {N}, gop_size {gop} "
+                             f"and bframes {nb}")
+        n_b = types.count("B")
+        if bmv is None or bmodes is None or len(bmv) != n_b or len(bmodes) != n_b:
+            raise ValueError("motion file: 'bmv_f32' / 'bmodes_u8' do not hold one entry per B-frame")
+        if bmodes.size and int(bmodes.max()) > 2:
+            raise ValueError(f"motion file: B-frame mode {int(bmodes.max())} (0, 1 or 2)")
+        bs = self.block_size_ME
+        kw = {"subpel": subpel} if subpel > 1 else {}
+        recon, p_idx, b_idx = {}, 0, 0
+        for i_idx, g0 in enumerate(range(0, N, gop)):
+            if i_idx >= len(meta["I_info"]):
+                break
+            recon[g0] = self._decode_frame(f"{in_prefix}_I_{i_idx}_enc")
+            for a, c in _anchor_intervals(types[g0:g0 + gop]):
+                rec_res = self._decode_frame(f"{in_prefix}_P_{p_idx}_enc")
+                recon[g0 + c] = K.reconstruct(K.motion_compensate(recon[g0 + a], mvs[p_idx], bs, **kw), rec_res)
+                p_idx += 1
+                for d in range(a + 1, c):
+                    rec_res = self._decode_frame(f"{in_prefix}_B_{b_idx}_enc")
+                    cf = K.motion_compensate(recon[g0 + a], bmv[b_idx, 0], bs, **kw)
+                    cb = K.motion_compensate(recon[g0 + c], bmv[b_idx, 1], bs, **kw)
+                    recon[g0 + d] = K.bipred_reconstruct(cf, cb, bmodes[b_idx], rec_res, bs)
+                    b_idx += 1
+        return [recon[i] for i in sorted(recon)]
+
+    def _write_decoded(self, out_prefix, recon):
         for idx, img in enumerate(recon):
             write_image(f"{out_prefix}_{idx:04d}.png", img)
         logging.warning("decoded MP4 not written (needs PyAV/imageio, not installed); PNG frames are")
@@ -294,7 +430,100 @@ class CoDec(_IPP, DCTCoDec):
             return _IPP._gop(self, frames, g0, i_idx, p0)
         return self._gop_resident(frames, g0, i_idx, p0)
 
+    def _gop_resident_bframes(self, frames, g0, i_idx, p0):
+        """_gop_bframes with the chain in HBM: both anchors' reconstructions stay on the device, a
+        B-frame is uploaded after its closing anchor is coded, and only the indices, the two
+        fields and the mode map come back."""
+        import ctypes
+        from concurrent.futures import ThreadPoolExecutor
+        from .. import _lib
+        from .. import dct as D
+        from ..device import DeviceBuffer, Stream
+        H, W = frames[g0].shape[:2]
+        bs, n = self.block_size_ME, H * W * 3
+        Hp, Wp = D.padded_shape(H, W, self.block_size)
+        hb, wb = H // bs, W // bs
+        types = gop_types(min(self.gop_size, len(frames) - g0), self.bframes)
+        n_b = self._b0(g0)
+        s = Stream()
+        cur, past, future, cf, cb, res, rec = (DeviceBuffer(n) for _ in range(7))
+        dk, dgray = DeviceBuffer(Hp * Wp * 3), DeviceBuffer(2 * H * W)
+        dmv, dmv_b, dmodes = DeviceBuffer(max(1, hb * wb * 8)), DeviceBuffer(max(1, hb * wb * 8)), \
+            DeviceBuffer(max(1, hb * wb))
+        q, flags, B = self.QSS, self.flags, self.block_size
+        call, sh = _lib.call, s.handle
+        sr, fast = int(self.search_range), int(bool(self.use_fast))
+
+        def upload(img):
+            a = np.ascontiguousarray(img, np.uint8)
+            if a.shape != (H, W, 3):
+                raise ValueError("IPP frames must share one H x W x 3 uint8 shape")
+            call("vcf_memcpy_htod", cur.ptr, a.ctypes.data_as(ctypes.c_void_p), n, sh)
+            s.synchronize()   # the host array may be freed after this
+
+        def code(src, base, pool, decode):
+            """transform + quantizer of src, indices to the host for the files; decode: decoder's frame -> rec."""
+            D.encode_device(src, 1, H, W, q, flags, out=dk, stream=s, block_size=B)
+            k = np.empty((Hp, Wp, 3), np.uint8)
+            call("vcf_memcpy_dtoh", k.ctypes.data_as(ctypes.c_void_p), dk.ptr, k.nbytes, sh)
+            if decode:
+                D.decode_device(dk, 1, H, W, q, flags, out=rec, stream=s, block_size=B)
+            s.synchronize()
+            return pool.submit(self._write_coded, base, k, (H, W, 3))
+
+        def predict(ref, field, comp):
+            """the search of cur in ref -> field (device), the compensation -> comp, the field -> host."""
+            if self.subpel > 1:
+                call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, H, W, bs, sr, fast, self.subpel, field.ptr,
+                     dgray.ptr, sh)
+                call("vcf_ipp_motion_compensate_qpel", ref.ptr, field.ptr, H, W, bs, comp.ptr, sh)
+            else:
+                call("vcf_ipp_block_match", ref.ptr, cur.ptr, H, W, bs, sr, fast, field.ptr, dgray.ptr, sh)
+                call("vcf_ipp_motion_compensate", ref.ptr, field.ptr, H, W, bs, comp.ptr, sh)
+            mv = np.zeros((hb, wb, 2), np.float32)
+            if mv.size:
+                call("vcf_memcpy_dtoh", mv.ctypes.data_as(ctypes.c_void_p), field.ptr, mv.nbytes, sh)
+            return mv
+
+        mvs, Bs = [], {"info": [], "mv": [], "modes": []}
+        try:
+            with ThreadPoolExecutor(max_workers=8) as pool:
+                upload(frames[g0])
+                fut_I = code(cur, f"{self.prefix}_I_{i_idx}_enc", pool, True)
+                call("vcf_memcpy_dtod", past.ptr, rec.ptr, n, sh)
+                futs_P, futs_B = [], []
+                for a, c in _anchor_intervals(types):
+                    upload(frames[g0 + c])
+                    mvs.append(predict(past, dmv, cf))
+                    call("vcf_ipp_residual", cur.ptr, cf.ptr, n, res.ptr, sh)
+                    futs_P.append(code(res, f"{self.prefix}_P_{p0 + len(futs_P)}_enc", pool, True))
+                    call("vcf_ipp_reconstruct", cf.ptr, rec.ptr, n, future.ptr, sh)
+                    for d in range(a + 1, c):
+                        upload(frames[g0 + d])
+                        mv_f, mv_b = predict(past, dmv, cf), predict(future, dmv_b, cb)
+                        call("vcf_ipp_bipred_residual", cur.ptr, cf.ptr, cb.ptr, H, W, bs, dmodes.ptr, res.ptr, sh)
+                        modes = np.zeros((hb, wb), np.uint8)
+                        if modes.size:
+                            call("vcf_memcpy_dtoh", modes.ctypes.data_as(ctypes.c_void_p), dmodes.ptr, modes.nbytes,
+                                 sh)
+                        futs_B.append(code(res, f"{self.prefix}_B_{n_b}_enc", pool, False))
+                        n_b += 1
+                        Bs["mv"].append(np.stack([mv_f, mv_b]))
+                        Bs["modes"].append(modes)
+                    past, future = future, past
+                s.synchronize()
+                I = {"bits": fut_I.result(), "idx": g0}
+                P = [{"bits": f.result()} for f in futs_P]
+                Bs["info"] = [{"bits": f.result()} for f in futs_B]
+        finally:
+            for b in (cur, past, future, cf, cb, res, rec, dk, dgray, dmv, dmv_b, dmodes):
+                b.free()
+            s.close()
+        return I, P, mvs, [], Bs
+
     def _gop_resident(self, frames, g0, i_idx, p0):
+        if self.bframes:
+            return self._gop_resident_bframes(frames, g0, i_idx, p0)
         import ctypes
         from concurrent.futures import ThreadPoolExecutor
         from .. import _lib

@@ -604,6 +604,9 @@ def add_ipp(enc, dec):
     enc.add_argument("--subpel", type=int, choices=(1, 2, 4), default=1,
                      help="Motion vector precision: 1 whole, 2 half, 4 quarter pel (default: 1; above 1 is not in "
                           "the reference, whose decoder cannot decode such streams)")
+    enc.add_argument("--bframes", type=int, choices=range(0, 8), default=0, metavar="N",
+                     help="B-frames between two anchors, 0 .. 7 (default: 0; above 0 is not in the reference, whose "
+                          "decoder cannot decode such streams; not with -R)")
     dec.add_argument("-i", "--input", type=str, default=IPP_OUTPUT, help=f"Input prefix (default: {IPP_OUTPUT})")
     dec.add_argument("-O", "--output", type=str, default="./ipp_decoded", help="Output prefix (default: ./ipp_decoded)")
     dec.add_argument("-N", "--number_of_frames", type=int, default=IPP_N_FRAMES,

@@ -149,3 +149,61 @@ def rdo_residual(cur: np.ndarray, comp: np.ndarray, modes: np.ndarray, bs: int =
 def rdo_reconstruct(comp: np.ndarray, rec: np.ndarray, modes: np.ndarray, bs: int = 16) -> np.ndarray:
     """Mode-aware P-frame reconstruction (IPP_DCT.py:512-526, 770-790)."""
     return _modal("vcf_ipp_rdo_reconstruct", comp, rec, modes, bs)
+
+
+def _check_bs(bs) -> int:
+    if not 1 <= int(bs) <= 64:
+        raise ValueError(f"block size {bs!r}: 1 .. 64")
+    return int(bs)
+
+
+def bipred_residual(cur: np.ndarray, cf: np.ndarray, cb: np.ndarray, bs: int = 16):
+    """B-frame decision and residual (vcf_ipp_bipred_residual; not in the reference): per full
+    block the argmin of (SAD, mode) over cf, cb and (cf + cb + 1) >> 1 -> ((H//bs, W//bs) u8
+    modes, clip(cur - pred + 128) over the whole frame, pred = 0 outside the full blocks)."""
+    cur, cf, cb = _rgb(cur), _rgb(cf), _rgb(cb)
+    bs = _check_bs(bs)
+    if not cur.shape == cf.shape == cb.shape:
+        raise ValueError("shape mismatch")
+    H, W = cur.shape[:2]
+    modes, res = np.zeros((H // bs, W // bs), np.uint8), np.empty_like(cur)
+    if res.size == 0:
+        return modes, res
+    dc, df, db = (DeviceBuffer.from_array(a) for a in (cur, cf, cb))
+    dm, do = DeviceBuffer(max(1, modes.nbytes)), DeviceBuffer(res.nbytes)
+    try:
+        L.call("vcf_ipp_bipred_residual", dc.ptr, df.ptr, db.ptr, H, W, bs, dm.ptr, do.ptr, None)
+        if modes.size:
+            dm.download(modes)
+        return modes, do.download(res)
+    finally:
+        for x in (dc, df, db, dm, do):
+            x.free()
+
+
+def bipred_reconstruct(cf: np.ndarray, cb: np.ndarray, modes: np.ndarray, rec: np.ndarray, bs: int = 16) -> np.ndarray:
+    """B-frame reconstruction (vcf_ipp_bipred_reconstruct): pred from the mode map (0 cf, 1 cb,
+    2 their rounded average; 0 outside the full blocks), then clip(pred + rec - 128)."""
+    cf, cb, rec = _rgb(cf), _rgb(cb), _rgb(rec)
+    bs = _check_bs(bs)
+    if not cf.shape == cb.shape == rec.shape:
+        raise ValueError("shape mismatch")
+    H, W = cf.shape[:2]
+    m = np.asarray(modes)
+    if m.dtype != np.uint8 or m.shape != (H // bs, W // bs):
+        raise ValueError(f"mode map {m.dtype} {m.shape} != uint8 {(H // bs, W // bs)}")
+    if m.size and int(m.max()) > 2:
+        raise ValueError(f"B-frame mode {int(m.max())}: 0 (forward), 1 (backward) or 2 (average)")
+    m = np.ascontiguousarray(m)
+    out = np.empty_like(cf)
+    if out.size == 0:
+        return out
+    df, db, dr, do = DeviceBuffer.from_array(cf), DeviceBuffer.from_array(cb), DeviceBuffer.from_array(rec), \
+        DeviceBuffer(out.nbytes)
+    dm = DeviceBuffer.from_array(m if m.size else np.zeros(1, np.uint8))
+    try:
+        L.call("vcf_ipp_bipred_reconstruct", df.ptr, db.ptr, dm.ptr, dr.ptr, H, W, bs, do.ptr, None)
+        return do.download(out)
+    finally:
+        for x in (df, db, dr, do, dm):
+            x.free()
