@@ -482,7 +482,58 @@ int vcf_ipp_block_match_subpel(const uint8_t *ref_rgb_dev, const uint8_t *cur_rg
                                int32_t sr, int32_t fast, int32_t subpel, float *mv_dev, uint8_t *gray_workspace_dev,
                                void *stream);
 
-/* Compensation of an arbitrary float field under the rule above:
+/* Hierarchical motion search (--me_levels; not in the reference).  Integers
+ * throughout; it changes only which vectors the encoder chooses.
+ * Level 0 is the u8 luma plane of the gray pass (A10), H_0 = H, W_0 = W.
+ * Level l + 1 has H_{l+1} = H_l >> 1, W_{l+1} = W_l >> 1 and
+ *   g_{l+1}[y, x] = (g_l[2y, 2x] + g_l[2y, 2x+1] + g_l[2y+1, 2x] + g_l[2y+1, 2x+1] + 2) >> 2
+ * (an odd last row or column is dropped); ref and cur both get a pyramid.
+ * levels = L in 0..3; L > 0 needs bs % (1 << L) == 0 and (bs >> L) >= 2.
+ * Block (by, bx) has side b_l = bs >> l and origin (by b_l, bx b_l) at level
+ * l; the field is the usual (H/bs) x (W/bs).  Every level-l block of a full
+ * level-0 block lies inside plane l: (by + 1) bs <= H gives
+ * (by + 1) b_l = ((by + 1) bs) >> l <= H >> l = H_l (bs is a multiple of 2^l),
+ * columns alike.  A candidate (dx, dy) at level l is valid iff the displaced
+ * b_l x b_l block lies inside plane l (H_l, W_l).
+ * Top level L: vcf_ipp_block_match's full search (same kernels, candidate
+ * order dy outer / dx inner from -sr, validity and first-strict-minimum tie
+ * rule) on the level-L planes with block side b_L and range sr -> v_L.
+ * Level l = L-1 .. 0: the centre is c = 2 v_{l+1}; it is valid, because
+ * 0 <= y and y + b_{l+1} <= H_{l+1} give 0 <= 2y and 2y + b_l <= 2 H_{l+1} <= H_l.
+ * The candidates are c + (ddx, ddy), ddx, ddy in {-1, 0, 1}; the winner v_l is
+ * the argmin of (SAD, index) with the centre at index 0 and the 8 neighbours
+ * 1..8 in ddy-outer / ddx-inner order, invalid neighbours skipped; SAD is the
+ * sum of |g^ref_l - g^cur_l| over the block.  v_0 is written as float32
+ * (dx, dy): it lies within +-(sr 2^L + 2^L - 1).  subpel in {2, 4}: 4 v_0 is
+ * the centre of the sub-pel stages above, which do not change.  L = 0 writes
+ * exactly what vcf_ipp_block_match (fast = 0) / vcf_ipp_block_match_subpel
+ * write.  The three-step search is not offered under L > 0.
+ * Workspace (vcf_ipp_hier_workspace_bytes; VCF_ERR_INVALID for H, W <= 0 or
+ * levels outside 0..3): sum over l = 0..L of 2 H_l W_l bytes -- level by
+ * level, ref's plane then cur's, back to back without padding, so the first
+ * 2*H*W bytes are the two gray planes as in vcf_ipp_block_match.  No
+ * per-level vectors are kept: the top level writes its field to mv_dev and
+ * the refinement rewrites it in place.
+ * Kernels: one pyramid launch per level (both frames; 4 output bytes per lane
+ * from two rows of 8, read as words where aligned), the full-search kernels
+ * on the top planes, one refinement launch for all of L-1 .. 0 (one wave per
+ * block; the block and the (b_l + 2)^2 window in LDS as words, v_alignbyte +
+ * v_sad_u8 where b_l % 4 == 0 and bytes otherwise, the 9 sums reduced three
+ * to a 64-bit word), then the sub-pel kernel when subpel > 1.
+ * Limits and alignment as vcf_ipp_block_match_subpel: bs <= 64, sr <= 32
+ * (at the top level), mv_dev 4-byte aligned, the frames and the workspace
+ * unaligned.  VCF_ERR_INVALID before any device work for a violation, levels
+ * outside 0..3, a bad bs / levels pair, subpel outside {1, 2, 4},
+ * workspace_bytes below the size function's, or a null pointer.  Written: the
+ * (H/bs) * (W/bs) * 2 floats at mv_dev and the first
+ * vcf_ipp_hier_workspace_bytes bytes of the workspace; an empty field (H < bs
+ * or W < bs) is legal and writes nothing. */
+int vcf_ipp_hier_workspace_bytes(int32_t H, int32_t W, int32_t levels, int64_t *bytes);
+int vcf_ipp_block_match_hier(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, int32_t bs,
+                             int32_t sr, int32_t levels, int32_t subpel, float *mv_dev, uint8_t *workspace_dev,
+                             int64_t workspace_bytes, void *stream);
+
+/* Compensation of an arbitrary float field under the sub-pel rule above:
  * q = lrintf(4 m) per component; an invalid vector falls back to the
  * co-located block, pixels outside the full-block area are 0 (both as
  * vcf_ipp_motion_compensate); for integer-valued fields the output equals

@@ -24,7 +24,7 @@ AB_SOURCES = ["ab/vcf_dct_dz_ab.hip", "ab/vcf_dwt_ab.hip", "ab/vcf_dwt_sched.hip
 # vcf_dwt: the entries ab/vcf_dwt_sched.hip calls)
 AB_LINK = ["vcf_runtime.hip", "vcf_dct_any.hip", "vcf_cbaac_gpu.hip", "vcf_cbaac.cpp", "vcf_ipp.hip", "vcf_dwt.hip"]
 SOURCES = ["vcf_runtime.hip", "vcf_dct_dz.hip", "vcf_dct_any.hip", "vcf_quant.hip", "vcf_dwt.hip", "vcf_cbaac.cpp",
-           "vcf_cbahc.cpp", "vcf_ipp.hip", "vcf_ipp_rdo.hip", "vcf_ipp_subpel.hip", "vcf_ipp_bipred.hip",
+           "vcf_cbahc.cpp", "vcf_ipp.hip", "vcf_ipp_rdo.hip", "vcf_ipp_subpel.hip", "vcf_ipp_hier.hip", "vcf_ipp_bipred.hip",
            "vcf_png.cpp", "vcf_comm.cpp", "vcf_cbaac_gpu.hip", "vcf_plugins.hip", "vcf_deflate.hip",
            "vcf_inflate.hip", "vcf_mdct_dz.hip", "vcf_klt_dz.hip", "vcf_vq.hip", "vcf_lbt.hip",
            "vcf_distortion.hip", "vcf_ssim.hip", "vcf_index_hist.hip", "vcf_dct_rdoq.hip", "vcf_deblock.hip"]

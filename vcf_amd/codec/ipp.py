@@ -35,6 +35,10 @@ future one or their average (vcf_amd/csrc/vcf_ipp_bipred.hip), and nothing
 predicts from a B-frame.  The B-frames go to {prefix}_B_{n}_enc files, their
 fields and mode maps to "bmv_f32" / "bmodes_u8" of the motion file, and
 meta.json carries "bframes", "frame_types" and "B_info".
+--me_levels L (not in the reference) makes every motion search coarse to fine
+on a luma pyramid (vcf_amd/csrc/vcf_ipp_hier.hip): -S applies on level L and
+the vectors reach +-(S 2^L + 2^L - 1).  It changes only the vectors chosen: no
+file, array or meta.json key is added, and the decoder does not know of it.
 """
 from __future__ import annotations
 
@@ -48,6 +52,7 @@ import struct
 import numpy as np
 
 from .. import ipp as K
+from ..ipp import check_levels, hier_workspace_bytes
 from . import shard
 from .dct2d import CoDec as DCTCoDec
 from .dwt2d import CoDec as DWTCoDec
@@ -151,6 +156,8 @@ class _IPP:
             raise ValueError(f"--bframes {self.bframes}: 0 .. {MAX_BFRAMES}")
         if self.bframes and self.rdo_lambda > 0:
             raise NotImplementedError("--bframes with -R: no mode-decision anchors beside B-frames yet")
+        # levels of the hierarchical motion search (not in the reference); the encoder's choice alone
+        self.me_levels = check_levels(int(getattr(args, "me_levels", 0) or 0), self.block_size_ME, self.use_fast)
         self.prefix = resolve_prefix(args.output) if getattr(args, "output", None) else None
         self.group = group if group is not None else shard.Group()
 
@@ -174,11 +181,12 @@ class _IPP:
         ref = recon_I
         for p in range(1, min(self.gop_size, len(frames) - g0)):
             cur = frames[g0 + p]
+            lv = {"levels": self.me_levels} if self.me_levels else {}   # at 0 the calls are what they were
             if self.subpel > 1:
-                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, subpel=self.subpel)
+                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, subpel=self.subpel, **lv)
                 comp = K.motion_compensate(ref, mv, bs, subpel=self.subpel)
             else:
-                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast)
+                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, **lv)
                 comp = K.motion_compensate(ref, mv, bs)
             if self.rdo_lambda > 0:
                 # :441-536: per-block I/P decision, the mixed-mode frame, its reconstruction
@@ -208,6 +216,7 @@ class _IPP:
         anchor before it) and the B-frames between in display order (predicted from both)."""
         bs, sr, fast = self.block_size_ME, self.search_range, self.use_fast
         kw = {"subpel": self.subpel} if self.subpel > 1 else {}
+        sw = {**kw, "levels": self.me_levels} if self.me_levels else kw   # the searches' keywords
         types = gop_types(min(self.gop_size, len(frames) - g0), self.bframes)
         n_b = self._b0(g0)
         recon_I, bits_I = self.encode_decode_proxy(frames[g0], "I", i_idx)
@@ -216,7 +225,7 @@ class _IPP:
         B = {"info": [], "mv": [], "modes": []}
         for a, c in _anchor_intervals(types):
             cur = frames[g0 + c]
-            mv = K.block_matching(recon[a], cur, bs, sr, fast, **kw)
+            mv = K.block_matching(recon[a], cur, bs, sr, fast, **sw)
             comp = K.motion_compensate(recon[a], mv, bs, **kw)
             rec_res, bits_P = self.encode_decode_proxy(K.residual(cur, comp), "P", p0 + len(P))
             recon[c] = K.reconstruct(comp, rec_res)
@@ -224,8 +233,8 @@ class _IPP:
             P.append({"bits": bits_P})
             for d in range(a + 1, c):
                 cur = frames[g0 + d]
-                mv_f = K.block_matching(recon[a], cur, bs, sr, fast, **kw)
-                mv_b = K.block_matching(recon[c], cur, bs, sr, fast, **kw)
+                mv_f = K.block_matching(recon[a], cur, bs, sr, fast, **sw)
+                mv_b = K.block_matching(recon[c], cur, bs, sr, fast, **sw)
                 cf = K.motion_compensate(recon[a], mv_f, bs, **kw)
                 cb = K.motion_compensate(recon[c], mv_b, bs, **kw)
                 modes, res = K.bipred_residual(cur, cf, cb, bs)
@@ -447,7 +456,8 @@ class CoDec(_IPP, DCTCoDec):
         n_b = self._b0(g0)
         s = Stream()
         cur, past, future, cf, cb, res, rec = (DeviceBuffer(n) for _ in range(7))
-        dk, dgray = DeviceBuffer(Hp * Wp * 3), DeviceBuffer(2 * H * W)
+        nws = hier_workspace_bytes(H, W, self.me_levels) if self.me_levels else 2 * H * W
+        dk, dgray = DeviceBuffer(Hp * Wp * 3), DeviceBuffer(nws)
         dmv, dmv_b, dmodes = DeviceBuffer(max(1, hb * wb * 8)), DeviceBuffer(max(1, hb * wb * 8)), \
             DeviceBuffer(max(1, hb * wb))
         q, flags, B = self.QSS, self.flags, self.block_size
@@ -473,7 +483,12 @@ class CoDec(_IPP, DCTCoDec):
 
         def predict(ref, field, comp):
             """the search of cur in ref -> field (device), the compensation -> comp, the field -> host."""
-            if self.subpel > 1:
+            if self.me_levels:
+                call("vcf_ipp_block_match_hier", ref.ptr, cur.ptr, H, W, bs, sr, self.me_levels, self.subpel,
+                     field.ptr, dgray.ptr, nws, sh)
+                call("vcf_ipp_motion_compensate_qpel" if self.subpel > 1 else "vcf_ipp_motion_compensate", ref.ptr,
+                     field.ptr, H, W, bs, comp.ptr, sh)
+            elif self.subpel > 1:
                 call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, H, W, bs, sr, fast, self.subpel, field.ptr,
                      dgray.ptr, sh)
                 call("vcf_ipp_motion_compensate_qpel", ref.ptr, field.ptr, H, W, bs, comp.ptr, sh)
@@ -535,7 +550,8 @@ class CoDec(_IPP, DCTCoDec):
         hb, wb = H // bs, W // bs
         s = Stream()
         cur, ref, comp, res, rec = (DeviceBuffer(n) for _ in range(5))
-        dk, dmv, dgray = DeviceBuffer(Hp * Wp * 3), DeviceBuffer(max(1, hb * wb * 8)), DeviceBuffer(2 * H * W)
+        nws = hier_workspace_bytes(H, W, self.me_levels) if self.me_levels else 2 * H * W
+        dk, dmv, dgray = DeviceBuffer(Hp * Wp * 3), DeviceBuffer(max(1, hb * wb * 8)), DeviceBuffer(nws)
         dmodes = DeviceBuffer(max(1, hb * wb))
         q, flags, B = self.QSS, self.flags, self.block_size
         call, sh = _lib.call, s.handle
@@ -565,7 +581,12 @@ class CoDec(_IPP, DCTCoDec):
                 futs = []
                 for p in range(1, min(self.gop_size, len(frames) - g0)):
                     upload(frames[g0 + p])
-                    if self.subpel > 1:
+                    if self.me_levels:
+                        call("vcf_ipp_block_match_hier", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
+                             self.me_levels, self.subpel, dmv.ptr, dgray.ptr, nws, sh)
+                        call("vcf_ipp_motion_compensate_qpel" if self.subpel > 1 else "vcf_ipp_motion_compensate",
+                             ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
+                    elif self.subpel > 1:
                         call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
                              int(bool(self.use_fast)), self.subpel, dmv.ptr, dgray.ptr, sh)
                         call("vcf_ipp_motion_compensate_qpel", ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)

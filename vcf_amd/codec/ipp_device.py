@@ -48,16 +48,19 @@ class _At:
 
 class DeviceIPP:
     """One rank's part of a GOP-sharded, HBM-resident IPP encode (2D-DCT,
-    deadzone Q, the reference's default -c TIFF), full search or --fast."""
+    deadzone Q, the reference's default -c TIFF), full search or --fast, or the
+    hierarchical search (levels > 0)."""
 
     def __init__(self, comm, rank: int, world: int, n_frames: int, H: int, W: int, Q: int = 32, gop: int = 10,
-                 bs: int = 16, sr: int = 8, fast: bool = False, subpel: int = 1):
+                 bs: int = 16, sr: int = 8, fast: bool = False, subpel: int = 1, levels: int = 0):
         self.comm, self.rank, self.world = comm, int(rank), int(world)
         self.N, self.H, self.W, self.Q = int(n_frames), int(H), int(W), int(Q)
         self.gop, self.bs, self.sr, self.fast = int(gop), int(bs), int(sr), bool(fast)
         if subpel not in (1, 2, 4):
             raise ValueError(f"subpel {subpel!r}: 1, 2 or 4")
         self.subpel = int(subpel)   # > 1: half / quarter-pel vectors and the bilinear compensator
+        from ..ipp import check_levels, hier_workspace_bytes
+        self.levels = check_levels(levels, self.bs, self.fast)   # > 0: the hierarchical search
         self.n_gops = (self.N + self.gop - 1) // self.gop
         self.g_lo, self.g_hi = frame_range(self.n_gops, self.rank, self.world)
 
@@ -88,7 +91,8 @@ class DeviceIPP:
         # fields stay in HBM through the GOP loop and come back in one copy after it
         self.mvb = self.hb * self.wb * 8
         self.mv = DeviceBuffer(max(1, max(1, self.n_local) * self.mvb))
-        self.gray = DeviceBuffer(2 * self.H * self.W)
+        self.gray_bytes = hier_workspace_bytes(self.H, self.W, self.levels) if self.levels else 2 * self.H * self.W
+        self.gray = DeviceBuffer(self.gray_bytes)
         self.out = DeviceBuffer(max(1, self.n_local * self.spf * self.slot))
         self.sizes = DeviceBuffer(max(4, self.n_local * self.spf * 4))
         self.ws = Z.workspace_buffer(max(1, self.n_local) * self.spf)
@@ -130,7 +134,12 @@ class DeviceIPP:
                     continue
                 ref, comp = _At(self.ref, g * fb, fb), _At(self.comp, g * fb, fb)
                 mv = _At(self.mv, f * self.mvb, self.mvb)
-                if self.subpel > 1:
+                if self.levels:
+                    call("vcf_ipp_block_match_hier", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr, self.levels,
+                         self.subpel, mv.ptr, self.gray.ptr, self.gray_bytes, sh)
+                    call("vcf_ipp_motion_compensate_qpel" if self.subpel > 1 else "vcf_ipp_motion_compensate", ref.ptr,
+                         mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
+                elif self.subpel > 1:
                     call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr,
                          int(self.fast), self.subpel, mv.ptr, self.gray.ptr, sh)
                     call("vcf_ipp_motion_compensate_qpel", ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)

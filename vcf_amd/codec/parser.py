@@ -607,6 +607,11 @@ def add_ipp(enc, dec):
     enc.add_argument("--bframes", type=int, choices=range(0, 8), default=0, metavar="N",
                      help="B-frames between two anchors, 0 .. 7 (default: 0; above 0 is not in the reference, whose "
                           "decoder cannot decode such streams; not with -R)")
+    enc.add_argument("--me_levels", type=int, choices=range(0, 4), default=0, metavar="L",
+                     help="Levels of the hierarchical motion search, 0 .. 3 (default: 0, the plain search): -S applies "
+                          "on a luma pyramid's level L and each finer level refines by +-1, covering "
+                          "+-(S*2^L + 2^L - 1) pixels; -M must be a multiple of 2^L and at least 2^(L+1); not with "
+                          "--fast; not in the reference, whose decoder still decodes such streams")
     dec.add_argument("-i", "--input", type=str, default=IPP_OUTPUT, help=f"Input prefix (default: {IPP_OUTPUT})")
     dec.add_argument("-O", "--output", type=str, default="./ipp_decoded", help="Output prefix (default: ./ipp_decoded)")
     dec.add_argument("-N", "--number_of_frames", type=int, default=IPP_N_FRAMES,

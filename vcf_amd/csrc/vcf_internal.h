@@ -92,6 +92,16 @@ int cbaac_tiled_decode_classes(int32_t kernel, const uint8_t *in_dev, const int6
 // Block matching (vcf_ipp.hip), variant: 0 = the word kernels where the block size allows, 1 = the byte kernels
 int ipp_block_match(int32_t variant, const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W,
                     int32_t bs, int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream);
+// Its two steps, for the hierarchical search (vcf_ipp_hier.hip): the gray pass of both frames (ref's
+// luma at gray_dev, cur's at gray_dev + H * W) and the search on two H x W luma planes; and the
+// sub-pel refinement of an integer field on two luma planes (vcf_ipp_subpel.hip).  Launches only:
+// the caller has checked the arguments and that the field is not empty.
+void ipp_gray_planes(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, uint8_t *gray_dev,
+                     void *stream);
+void ipp_plane_search(int32_t variant, const uint8_t *ref_gray_dev, const uint8_t *cur_gray_dev, int32_t H, int32_t W,
+                      int32_t bs, int32_t sr, int32_t fast, float *mv_dev, void *stream);
+void ipp_subpel_refine(const uint8_t *ref_gray_dev, const uint8_t *cur_gray_dev, int32_t H, int32_t W, int32_t bs,
+                       int32_t subpel, float *mv_dev, void *stream);
 
 // The kernel schedule of one 2D-DWT call (vcf_dwt.hip); the defaults are the library's rules.  The
 // product entry points pass DwtSchedule{}; the A/B library's vcf_dwt_dz_*_sched twins

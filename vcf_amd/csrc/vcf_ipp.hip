@@ -432,23 +432,26 @@ unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
-// variant 0: the word kernels when bs % 4 == 0 (full search) or bs == 16 (three-step); 1: the byte
-// kernels (vcf_ipp_block_match_variant of the A/B library)
-int ipp_block_match(int32_t variant, const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W,
-                    int32_t bs, int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream)
+// The gray pass of both frames: ref's luma at gray_dev, cur's at gray_dev + H * W.
+void ipp_gray_planes(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, uint8_t *gray_dev,
+                     void *stream)
 {
-    if (!ref_rgb_dev || !cur_rgb_dev || !mv_dev || !gray_workspace_dev) return set_error(VCF_ERR_INVALID, "null buffer");
-    VCF_REQUIRE_ALIGNED(mv_dev, 4);
-    if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad frame shape");
-    if (bs < 1 || bs > kMaxBs) return set_error(VCF_ERR_UNSUPPORTED, "block size %d (1..%d)", bs, kMaxBs);
-    if (sr < 0 || sr > kMaxSr) return set_error(VCF_ERR_UNSUPPORTED, "search range %d (0..%d)", sr, kMaxSr);
-    const int nbx = W / bs, nby = H / bs;
-    if (nbx == 0 || nby == 0) return VCF_OK;
     hipStream_t s = (hipStream_t)stream;
     const long long npx = (long long)H * W;
-    uint8_t *rg = gray_workspace_dev, *cg = gray_workspace_dev + npx;
-    hipLaunchKernelGGL(ipp_gray_kernel, dim3(blocks_for(npx)), dim3(256), 0, s, ref_rgb_dev, rg, npx);
-    hipLaunchKernelGGL(ipp_gray_kernel, dim3(blocks_for(npx)), dim3(256), 0, s, cur_rgb_dev, cg, npx);
+    hipLaunchKernelGGL(ipp_gray_kernel, dim3(blocks_for(npx)), dim3(256), 0, s, ref_rgb_dev, gray_dev, npx);
+    hipLaunchKernelGGL(ipp_gray_kernel, dim3(blocks_for(npx)), dim3(256), 0, s, cur_rgb_dev, gray_dev + npx, npx);
+}
+
+// The search on two H x W luma planes (row stride W), one vector per full bs x bs block: the launch
+// vcf_ipp_block_match makes after its gray pass, and the top level of the hierarchical search on a
+// pyramid plane.  variant 0: the word kernels when bs % 4 == 0 (full search) or bs == 16
+// (three-step); 1: the byte kernels (vcf_ipp_block_match_variant of the A/B library).  The caller
+// has checked bs, sr and that the field is not empty.
+void ipp_plane_search(int32_t variant, const uint8_t *rg, const uint8_t *cg, int32_t H, int32_t W, int32_t bs,
+                      int32_t sr, int32_t fast, float *mv_dev, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const int nbx = W / bs, nby = H / bs;
     if (fast) {
         if (bs == 16 && variant == 0)
             hipLaunchKernelGGL(ipp_tss16_kernel, dim3(nbx, nby), dim3(64), 0, s, rg, cg, H, W, sr, mv_dev);
@@ -468,6 +471,20 @@ int ipp_block_match(int32_t variant, const uint8_t *ref_rgb_dev, const uint8_t *
         default: hipLaunchKernelGGL(ipp_full_search_words<0>, grid, dim3(nthr), 0, s, rg, cg, H, W, bs, sr, mv_dev); break;
         }
     }
+}
+
+int ipp_block_match(int32_t variant, const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W,
+                    int32_t bs, int32_t sr, int32_t fast, float *mv_dev, uint8_t *gray_workspace_dev, void *stream)
+{
+    if (!ref_rgb_dev || !cur_rgb_dev || !mv_dev || !gray_workspace_dev) return set_error(VCF_ERR_INVALID, "null buffer");
+    VCF_REQUIRE_ALIGNED(mv_dev, 4);
+    if (H <= 0 || W <= 0) return set_error(VCF_ERR_INVALID, "bad frame shape");
+    if (bs < 1 || bs > kMaxBs) return set_error(VCF_ERR_UNSUPPORTED, "block size %d (1..%d)", bs, kMaxBs);
+    if (sr < 0 || sr > kMaxSr) return set_error(VCF_ERR_UNSUPPORTED, "search range %d (0..%d)", sr, kMaxSr);
+    if (W / bs == 0 || H / bs == 0) return VCF_OK;
+    ipp_gray_planes(ref_rgb_dev, cur_rgb_dev, H, W, gray_workspace_dev, stream);
+    ipp_plane_search(variant, gray_workspace_dev, gray_workspace_dev + (long long)H * W, H, W, bs, sr, fast, mv_dev,
+                     stream);
     return hip_check(hipGetLastError(), "ipp block match launch");
 }
 }  // namespace vcf

@@ -211,6 +211,13 @@ __global__ __launch_bounds__(256) void ipp_mc_qpel_kernel(const uint8_t *__restr
 }
 
 }  // namespace
+
+void ipp_subpel_refine(const uint8_t *ref_gray_dev, const uint8_t *cur_gray_dev, int32_t H, int32_t W, int32_t bs,
+                       int32_t subpel, float *mv_dev, void *stream)
+{
+    hipLaunchKernelGGL(ipp_subpel_refine_kernel, dim3(W / bs, H / bs), dim3(64), 0, (hipStream_t)stream, ref_gray_dev,
+                       cur_gray_dev, H, W, bs, subpel, mv_dev);
+}
 }  // namespace vcf
 
 using namespace vcf;
@@ -229,9 +236,7 @@ int vcf_ipp_block_match_subpel(const uint8_t *ref_rgb_dev, const uint8_t *cur_rg
     if (rc != VCF_OK || subpel == 1) return rc;
     const int nbx = W / bs, nby = H / bs;
     if (nbx == 0 || nby == 0) return VCF_OK;
-    const long long npx = (long long)H * W;
-    hipLaunchKernelGGL(ipp_subpel_refine_kernel, dim3(nbx, nby), dim3(64), 0, (hipStream_t)stream, gray_workspace_dev,
-                       gray_workspace_dev + npx, H, W, bs, subpel, mv_dev);
+    ipp_subpel_refine(gray_workspace_dev, gray_workspace_dev + (long long)H * W, H, W, bs, subpel, mv_dev, stream);
     return hip_check(hipGetLastError(), "ipp sub-pel refinement launch");
 }
 

@@ -23,15 +23,44 @@ def _check_subpel(subpel) -> int:
     return int(subpel)
 
 
+MAX_LEVELS = 3
+
+
+def check_levels(levels, bs, fast=False) -> int:
+    """The levels of the hierarchical search (include/vcf_amd.h): 0 .. 3, with bs a multiple of
+    2^levels and bs >> levels >= 2, and not with the three-step search."""
+    if isinstance(levels, bool) or levels not in range(MAX_LEVELS + 1):
+        raise ValueError(f"levels {levels!r}: 0 .. {MAX_LEVELS}")
+    levels = int(levels)
+    if levels and (int(bs) % (1 << levels) or (int(bs) >> levels) < 2):
+        raise ValueError(f"block size {bs} with {levels} levels: a multiple of {1 << levels}, at least {2 << levels}")
+    if levels and fast:
+        raise ValueError("the three-step search (fast) is a whole-frame tool: not with levels > 0")
+    return levels
+
+
+def hier_workspace_bytes(H: int, W: int, levels: int) -> int:
+    """vcf_ipp_hier_workspace_bytes: the two gray planes and both pyramids."""
+    import ctypes
+    n = ctypes.c_int64(0)
+    L.call("vcf_ipp_hier_workspace_bytes", int(H), int(W), int(levels), ctypes.byref(n))
+    return int(n.value)
+
+
 def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, fast: bool = False,
-                   variant: int = 0, subpel: int = 1) -> np.ndarray:
+                   variant: int = 0, subpel: int = 1, levels: int = 0) -> np.ndarray:
     """IPP.block_matching (IPP_DCT.py:344-376) -> (H//bs, W//bs, 2) float32 (dx, dy).
     variant 0: word kernels (full search for bs % 4 == 0, parallel-round TSS for bs 16; the product's rule),
     1: byte / serial kernels (the A/B library's twin; same vectors).
     subpel 2 / 4: the integer search refined to half / quarter pel (vcf_ipp_block_match_subpel;
-    not in the reference), vectors in multiples of 1/subpel."""
+    not in the reference), vectors in multiples of 1/subpel.
+    levels 1 .. 3: the coarse-to-fine search on a luma pyramid (vcf_ipp_block_match_hier; not in the
+    reference), sr applied at the top level: vectors within +-(sr 2^levels + 2^levels - 1)."""
     ref, cur = _rgb(ref), _rgb(cur)
     subpel = _check_subpel(subpel)
+    levels = check_levels(levels, bs, fast)
+    if levels and variant != 0:
+        raise ValueError("the hierarchical search runs the product's integer kernels (variant 0)")
     if subpel > 1 and variant != 0:
         raise ValueError("the sub-pel search runs after the product's integer kernels (variant 0)")
     H, W = ref.shape[:2]
@@ -39,9 +68,13 @@ def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, 
     if mv.size == 0:
         return mv
     dr, dc = DeviceBuffer.from_array(ref), DeviceBuffer.from_array(cur)
-    dm, dg = DeviceBuffer(mv.nbytes), DeviceBuffer(2 * H * W)
+    nws = hier_workspace_bytes(H, W, levels) if levels else 2 * H * W
+    dm, dg = DeviceBuffer(mv.nbytes), DeviceBuffer(nws)
     try:
-        if subpel > 1:
+        if levels:
+            L.call("vcf_ipp_block_match_hier", dr.ptr, dc.ptr, H, W, int(bs), int(sr), levels, subpel, dm.ptr, dg.ptr,
+                   nws, None)
+        elif subpel > 1:
             L.call("vcf_ipp_block_match_subpel", dr.ptr, dc.ptr, H, W, int(bs), int(sr), int(bool(fast)), subpel,
                    dm.ptr, dg.ptr, None)
         else:
