@@ -544,6 +544,51 @@ int vcf_ipp_block_match_hier(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_
 int vcf_ipp_motion_compensate_qpel(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,
                                    uint8_t *out_rgb_dev, void *stream);
 
+/* Overlapped block motion compensation (--obmc; not in the reference).
+ * Integers throughout.  r is the H x W x 3 u8 reference, mv the (H/bs) x (W/bs)
+ * x 2 float32 field (dx, dy), bs in {4, 8, 16, 32, 64}; nby = H / bs,
+ * nbx = W / bs.
+ * 1. Block vectors in quarter pels: q = rint(4 m) per component (half to even),
+ *    clamped to +-2^28, a NaN gives -2^28 (as vcf_ipp_motion_compensate_qpel).
+ *    The vector of block (by, bx) is valid iff it is valid under "Sub-pel
+ *    motion" for the block's own origin (i, j) = (by bs, bx bs), X = 4 j + qx,
+ *    Y = 4 i + qy.  An invalid vector is replaced by (0, 0) everywhere the
+ *    block contributes.
+ * 2. Sample: P(q; y, x) is the bilinear sample of "Sub-pel motion" at
+ *    X = 4 x + qx, Y = 4 y + qy: ix = X >> 2, fx = X & 3, iy, fy alike, weights
+ *    (4-fx)(4-fy), fx (4-fy), (4-fx) fy, fx fy, rounded with + 8 >> 4.  Each of
+ *    the four tap coordinates is clamped to the frame: rows clamp(iy, 0, H-1)
+ *    and clamp(iy+1, 0, H-1), columns alike with W.  A valid vector at a pixel
+ *    of its own block never clamps, so P equals the sub-pel compensator's sample
+ *    there; a neighbour's vector, applied up to bs/2 pixels outside its own
+ *    block, may clamp.
+ * 3. Contributors of pixel (y, x) of block (by, bx), v = y - by bs,
+ *    u = x - bx bs: the horizontal neighbour is block column bx - 1 if
+ *    u < bs/2, else bx + 1, clamped to [0, nbx-1] (at a frame-border block the
+ *    neighbour is the block itself); the vertical neighbour row alike from v
+ *    and nby; the diagonal contributor is the block at (vertical neighbour row,
+ *    horizontal neighbour column).
+ * 4. Weights: the own weight is wx = bs + 2u + 1 if u < bs/2, else
+ *    3 bs - 2u - 1; the neighbour's is 2 bs - wx.  wy alike from v.
+ * 5. Blend, per channel: acc = sum over the four (row a, column b) choices of
+ *    wy_a wx_b P(q[a, b]; y, x); out = (acc + 2 bs^2) >> (2 log2(bs) + 2).
+ *    acc <= 255 * 4 * 64^2 fits in 32 bits.
+ * 6. Pixels with y >= nby bs or x >= nbx bs are 0, as in the other compensators.
+ * Where the four contributors of a pixel carry the same vector the output
+ * equals vcf_ipp_motion_compensate_qpel's; a uniform valid field, or a
+ * single-block frame, reproduces that compensator byte for byte.
+ * Kernel: a thread makes 4 consecutive bytes of a row, as the quarter-pel
+ * kernel does; a workgroup first resolves step 1 for its two block rows into
+ * LDS, once per block; samples come from aligned words where the reference is
+ * 4-byte aligned and no tap clamps, else byte by byte.
+ * The frames need no alignment; mv_dev must be 4-byte aligned.
+ * VCF_ERR_INVALID before any device work for a null buffer, a misaligned
+ * mv_dev, H or W <= 0, or bs outside {4, 8, 16, 32, 64}; VCF_ERR_UNSUPPORTED
+ * for H > 65535.  Writes the H * W * 3 bytes at out_rgb_dev; an empty field
+ * (nby or nbx = 0) yields a zero frame and mv_dev is not read. */
+int vcf_ipp_motion_compensate_obmc(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,
+                                   uint8_t *out_rgb_dev, void *stream);
+
 /* residual_shifted = clip(cur - comp + 128, 0, 255) (IPP_DCT.py:547-551).  No
  * pointer needs alignment; writes the n bytes at out_dev. */
 int vcf_ipp_residual(const uint8_t *cur_dev, const uint8_t *comp_dev, int64_t n, uint8_t *out_dev, void *stream);

@@ -145,6 +145,7 @@ SIGNATURES = {
     "vcf_ipp_motion_compensate": [_P, _P, _I32, _I32, _I32, _P, _P],
     "vcf_ipp_block_match_subpel": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
     "vcf_ipp_motion_compensate_qpel": [_P, _P, _I32, _I32, _I32, _P, _P],
+    "vcf_ipp_motion_compensate_obmc": [_P, _P, _I32, _I32, _I32, _P, _P],
     "vcf_ipp_hier_workspace_bytes": [_I32, _I32, _I32, ctypes.POINTER(_I64)],
     "vcf_ipp_block_match_hier": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P],
     "vcf_ipp_residual": [_P, _P, _I64, _P, _P],

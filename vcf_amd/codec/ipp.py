@@ -39,6 +39,11 @@ meta.json carries "bframes", "frame_types" and "B_info".
 on a luma pyramid (vcf_amd/csrc/vcf_ipp_hier.hip): -S applies on level L and
 the vectors reach +-(S 2^L + 2^L - 1).  It changes only the vectors chosen: no
 file, array or meta.json key is added, and the decoder does not know of it.
+--obmc (not in the reference) replaces every motion compensation, the B-frames'
+two included, by the overlapped one (vcf_amd/csrc/vcf_ipp_obmc.hip): a pixel is
+blended from its own block's vector and its nearest neighbours'.  -M must be 4,
+8, 16, 32 or 64; the searches, the motion file and the file names do not change;
+meta.json carries "obmc": true and the decoder compensates alike.
 """
 from __future__ import annotations
 
@@ -52,7 +57,7 @@ import struct
 import numpy as np
 
 from .. import ipp as K
-from ..ipp import check_levels, hier_workspace_bytes
+from ..ipp import check_levels, check_obmc_bs, hier_workspace_bytes, mc_entry
 from . import shard
 from .dct2d import CoDec as DCTCoDec
 from .dwt2d import CoDec as DWTCoDec
@@ -158,6 +163,13 @@ class _IPP:
             raise NotImplementedError("--bframes with -R: no mode-decision anchors beside B-frames yet")
         # levels of the hierarchical motion search (not in the reference); the encoder's choice alone
         self.me_levels = check_levels(int(getattr(args, "me_levels", 0) or 0), self.block_size_ME, self.use_fast)
+        # overlapped block motion compensation (not in the reference); the decoder takes it from meta.json
+        self.obmc = bool(getattr(args, "obmc", False))
+        if self.obmc:
+            try:
+                check_obmc_bs(self.block_size_ME)
+            except ValueError:
+                raise ValueError(f"--obmc with -M {self.block_size_ME}: -M must be 4, 8, 16, 32 or 64") from None
         self.prefix = resolve_prefix(args.output) if getattr(args, "output", None) else None
         self.group = group if group is not None else shard.Group()
 
@@ -182,12 +194,13 @@ class _IPP:
         for p in range(1, min(self.gop_size, len(frames) - g0)):
             cur = frames[g0 + p]
             lv = {"levels": self.me_levels} if self.me_levels else {}   # at 0 the calls are what they were
+            ob = {"obmc": True} if self.obmc else {}                    # and without --obmc
             if self.subpel > 1:
                 mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, subpel=self.subpel, **lv)
-                comp = K.motion_compensate(ref, mv, bs, subpel=self.subpel)
+                comp = K.motion_compensate(ref, mv, bs, subpel=self.subpel, **ob)
             else:
                 mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, **lv)
-                comp = K.motion_compensate(ref, mv, bs)
+                comp = K.motion_compensate(ref, mv, bs, **ob)
             if self.rdo_lambda > 0:
                 # :441-536: per-block I/P decision, the mixed-mode frame, its reconstruction
                 modes = K.rdo_modes(cur, comp, bs, self.QSS, self.rdo_lambda)
@@ -217,6 +230,7 @@ class _IPP:
         bs, sr, fast = self.block_size_ME, self.search_range, self.use_fast
         kw = {"subpel": self.subpel} if self.subpel > 1 else {}
         sw = {**kw, "levels": self.me_levels} if self.me_levels else kw   # the searches' keywords
+        cw = {**kw, "obmc": True} if self.obmc else kw                    # the compensations'
         types = gop_types(min(self.gop_size, len(frames) - g0), self.bframes)
         n_b = self._b0(g0)
         recon_I, bits_I = self.encode_decode_proxy(frames[g0], "I", i_idx)
@@ -226,7 +240,7 @@ class _IPP:
         for a, c in _anchor_intervals(types):
             cur = frames[g0 + c]
             mv = K.block_matching(recon[a], cur, bs, sr, fast, **sw)
-            comp = K.motion_compensate(recon[a], mv, bs, **kw)
+            comp = K.motion_compensate(recon[a], mv, bs, **cw)
             rec_res, bits_P = self.encode_decode_proxy(K.residual(cur, comp), "P", p0 + len(P))
             recon[c] = K.reconstruct(comp, rec_res)
             mvs.append(mv)
@@ -235,8 +249,8 @@ class _IPP:
                 cur = frames[g0 + d]
                 mv_f = K.block_matching(recon[a], cur, bs, sr, fast, **sw)
                 mv_b = K.block_matching(recon[c], cur, bs, sr, fast, **sw)
-                cf = K.motion_compensate(recon[a], mv_f, bs, **kw)
-                cb = K.motion_compensate(recon[c], mv_b, bs, **kw)
+                cf = K.motion_compensate(recon[a], mv_f, bs, **cw)
+                cb = K.motion_compensate(recon[c], mv_b, bs, **cw)
                 modes, res = K.bipred_residual(cur, cf, cb, bs)
                 _, bits_B = self.encode_decode_proxy(res, "B", n_b)   # nothing predicts from a B-frame
                 n_b += 1
@@ -316,6 +330,8 @@ class _IPP:
                 "mv_file": f"{os.path.basename(self.prefix)}_mv.npz", "base_prefix": os.path.basename(self.prefix)}
         if self.subpel > 1:
             meta["subpel"] = self.subpel   # fractional vectors: the decoder must interpolate
+        if self.obmc:
+            meta["obmc"] = True   # overlapped compensation: the decoder must blend alike
         if nb:
             meta["bframes"] = nb
             meta["frame_types"] = sequence_types(self.N_frames, self.gop_size, nb)
@@ -346,8 +362,15 @@ class _IPP:
         gop, N = meta["gop_size"], meta["n_frames"]
         bs = self.block_size_ME
         subpel = int(meta.get("subpel", 1))
+        obmc = bool(meta.get("obmc", False))
+        if obmc:
+            try:
+                check_obmc_bs(bs)
+            except ValueError:
+                raise ValueError(f"meta.json: obmc with -M {bs}: -M must be 4, 8, 16, 32 or 64") from None
+        ob = {"obmc": True} if obmc else {}
         if "bframes" in meta:
-            recon = self._decode_bframes(meta, in_prefix, mvs, bmv, bmodes, subpel)
+            recon = self._decode_bframes(meta, in_prefix, mvs, bmv, bmodes, subpel, obmc)
             return self._write_decoded(out_prefix, recon)
         recon, p_idx = [], 0
         for i_idx, g0 in enumerate(range(0, N, gop)):
@@ -357,8 +380,8 @@ class _IPP:
             recon.append(ref)
             for p in range(1, min(gop, N - g0)):
                 rec_res = self._decode_frame(f"{in_prefix}_P_{p_idx}_enc")
-                pred = K.motion_compensate(ref, mvs[p_idx], bs, subpel=subpel) if subpel > 1 else \
-                    K.motion_compensate(ref, mvs[p_idx], bs)
+                pred = K.motion_compensate(ref, mvs[p_idx], bs, subpel=subpel, **ob) if subpel > 1 else \
+                    K.motion_compensate(ref, mvs[p_idx], bs, **ob)
                 if modes is not None:   # RDO was used: mode-aware reconstruction (:770-790)
                     ref = K.rdo_reconstruct(pred, rec_res, modes[p_idx], bs)
                 else:
@@ -367,7 +390,7 @@ class _IPP:
                 p_idx += 1
         return self._write_decoded(out_prefix, recon)
 
-    def _decode_bframes(self, meta, in_prefix, mvs, bmv, bmodes, subpel):
+    def _decode_bframes(self, meta, in_prefix, mvs, bmv, bmodes, subpel, obmc=False):
         """The frames of a --bframes stream in display order: per GOP the I-frame, then per anchor
         interval the closing anchor and the B-frames between."""
         gop, N, nb = meta["gop_size"], meta["n_frames"], meta["bframes"]
@@ -384,6 +407,8 @@ class _IPP:
             raise ValueError(f"motion file: B-frame mode {int(bmodes.max())} (0, 1 or 2)")
         bs = self.block_size_ME
         kw = {"subpel": subpel} if subpel > 1 else {}
+        if obmc:
+            kw["obmc"] = True
         recon, p_idx, b_idx = {}, 0, 0
         for i_idx, g0 in enumerate(range(0, N, gop)):
             if i_idx >= len(meta["I_info"]):
@@ -486,15 +511,12 @@ class CoDec(_IPP, DCTCoDec):
             if self.me_levels:
                 call("vcf_ipp_block_match_hier", ref.ptr, cur.ptr, H, W, bs, sr, self.me_levels, self.subpel,
                      field.ptr, dgray.ptr, nws, sh)
-                call("vcf_ipp_motion_compensate_qpel" if self.subpel > 1 else "vcf_ipp_motion_compensate", ref.ptr,
-                     field.ptr, H, W, bs, comp.ptr, sh)
             elif self.subpel > 1:
                 call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, H, W, bs, sr, fast, self.subpel, field.ptr,
                      dgray.ptr, sh)
-                call("vcf_ipp_motion_compensate_qpel", ref.ptr, field.ptr, H, W, bs, comp.ptr, sh)
             else:
                 call("vcf_ipp_block_match", ref.ptr, cur.ptr, H, W, bs, sr, fast, field.ptr, dgray.ptr, sh)
-                call("vcf_ipp_motion_compensate", ref.ptr, field.ptr, H, W, bs, comp.ptr, sh)
+            call(mc_entry(self.subpel, self.obmc), ref.ptr, field.ptr, H, W, bs, comp.ptr, sh)
             mv = np.zeros((hb, wb, 2), np.float32)
             if mv.size:
                 call("vcf_memcpy_dtoh", mv.ctypes.data_as(ctypes.c_void_p), field.ptr, mv.nbytes, sh)
@@ -584,16 +606,13 @@ class CoDec(_IPP, DCTCoDec):
                     if self.me_levels:
                         call("vcf_ipp_block_match_hier", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
                              self.me_levels, self.subpel, dmv.ptr, dgray.ptr, nws, sh)
-                        call("vcf_ipp_motion_compensate_qpel" if self.subpel > 1 else "vcf_ipp_motion_compensate",
-                             ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
                     elif self.subpel > 1:
                         call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
                              int(bool(self.use_fast)), self.subpel, dmv.ptr, dgray.ptr, sh)
-                        call("vcf_ipp_motion_compensate_qpel", ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
                     else:
                         call("vcf_ipp_block_match", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
                              int(bool(self.use_fast)), dmv.ptr, dgray.ptr, sh)
-                        call("vcf_ipp_motion_compensate", ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
+                    call(mc_entry(self.subpel, self.obmc), ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
                     mv = np.zeros((hb, wb, 2), np.float32)
                     if mv.size:
                         call("vcf_memcpy_dtoh", mv.ctypes.data_as(ctypes.c_void_p), dmv.ptr, mv.nbytes, sh)

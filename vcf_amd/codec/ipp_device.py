@@ -49,18 +49,23 @@ class _At:
 class DeviceIPP:
     """One rank's part of a GOP-sharded, HBM-resident IPP encode (2D-DCT,
     deadzone Q, the reference's default -c TIFF), full search or --fast, or the
-    hierarchical search (levels > 0)."""
+    hierarchical search (levels > 0); obmc: the overlapped compensator (bs 4, 8, 16, 32 or 64)."""
 
     def __init__(self, comm, rank: int, world: int, n_frames: int, H: int, W: int, Q: int = 32, gop: int = 10,
-                 bs: int = 16, sr: int = 8, fast: bool = False, subpel: int = 1, levels: int = 0):
+                 bs: int = 16, sr: int = 8, fast: bool = False, subpel: int = 1, levels: int = 0,
+                 obmc: bool = False):
         self.comm, self.rank, self.world = comm, int(rank), int(world)
         self.N, self.H, self.W, self.Q = int(n_frames), int(H), int(W), int(Q)
         self.gop, self.bs, self.sr, self.fast = int(gop), int(bs), int(sr), bool(fast)
         if subpel not in (1, 2, 4):
             raise ValueError(f"subpel {subpel!r}: 1, 2 or 4")
         self.subpel = int(subpel)   # > 1: half / quarter-pel vectors and the bilinear compensator
-        from ..ipp import check_levels, hier_workspace_bytes
+        from ..ipp import check_levels, check_obmc_bs, hier_workspace_bytes, mc_entry
         self.levels = check_levels(levels, self.bs, self.fast)   # > 0: the hierarchical search
+        self.obmc = bool(obmc)
+        if self.obmc:
+            check_obmc_bs(self.bs)
+        self.mc = mc_entry(self.subpel, self.obmc)   # the compensator's entry point
         self.n_gops = (self.N + self.gop - 1) // self.gop
         self.g_lo, self.g_hi = frame_range(self.n_gops, self.rank, self.world)
 
@@ -137,16 +142,13 @@ class DeviceIPP:
                 if self.levels:
                     call("vcf_ipp_block_match_hier", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr, self.levels,
                          self.subpel, mv.ptr, self.gray.ptr, self.gray_bytes, sh)
-                    call("vcf_ipp_motion_compensate_qpel" if self.subpel > 1 else "vcf_ipp_motion_compensate", ref.ptr,
-                         mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
                 elif self.subpel > 1:
                     call("vcf_ipp_block_match_subpel", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr,
                          int(self.fast), self.subpel, mv.ptr, self.gray.ptr, sh)
-                    call("vcf_ipp_motion_compensate_qpel", ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
                 else:
                     call("vcf_ipp_block_match", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr, int(self.fast),
                          mv.ptr, self.gray.ptr, sh)
-                    call("vcf_ipp_motion_compensate", ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
+                call(self.mc, ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
                 call("vcf_ipp_residual", cur.ptr, comp.ptr, fb, self.res.address(j * fb), sh)
                 p_frames.append(f)
             n = len(gs)

@@ -612,6 +612,10 @@ def add_ipp(enc, dec):
                           "on a luma pyramid's level L and each finer level refines by +-1, covering "
                           "+-(S*2^L + 2^L - 1) pixels; -M must be a multiple of 2^L and at least 2^(L+1); not with "
                           "--fast; not in the reference, whose decoder still decodes such streams")
+    enc.add_argument("--obmc", action="store_true",
+                     help="Overlapped block motion compensation: blend each pixel from its own block's vector and its "
+                          "nearest neighbours' (default: off; not in the reference, whose decoder cannot decode such "
+                          "streams; -M must be 4, 8, 16, 32 or 64)")
     dec.add_argument("-i", "--input", type=str, default=IPP_OUTPUT, help=f"Input prefix (default: {IPP_OUTPUT})")
     dec.add_argument("-O", "--output", type=str, default="./ipp_decoded", help="Output prefix (default: ./ipp_decoded)")
     dec.add_argument("-N", "--number_of_frames", type=int, default=IPP_N_FRAMES,

@@ -17,24 +17,13 @@
 
 #include "vcf_amd.h"
 #include "vcf_internal.h"
+#include "vcf_ipp_qpel.h"   // bilinear, axis_valid, quarter_pels, seven_bytes
 
 namespace vcf {
 namespace {
 
 constexpr int kMaxBs = 64;
 constexpr int kMaxSr = 32;
-
-__device__ __forceinline__ uint32_t bilinear(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t fx, uint32_t fy)
-{
-    return ((4 - fx) * (4 - fy) * a + fx * (4 - fy) * b + (4 - fx) * fy * c + fx * fy * d + 8) >> 4;
-}
-
-// ix >= 0 and ix + bs + (fx ? 1 : 0) <= n for X = 4 ix + fx
-__device__ __forceinline__ bool axis_valid(long long X, int bs, int n)
-{
-    const long long ix = X >> 2;
-    return ix >= 0 && ix + bs + ((X & 3) ? 1 : 0) <= n;
-}
 
 // Refinement around the integer winner that mv holds: one wave per block.  The
 // block of cur and the (bs + 2)^2 luma window of ref around the integer winner
@@ -122,12 +111,6 @@ struct QpelBlock {
     uint32_t fy, fx;
 };
 
-__device__ __forceinline__ int quarter_pels(float m)
-{
-    const float f = fminf(fmaxf(rintf(4.f * m), -268435456.f), 268435456.f);   // +-2^28; fmaxf drops a NaN
-    return (int)f;
-}
-
 __device__ __forceinline__ QpelBlock qpel_block(const float *__restrict__ mv, int nbx, int by, int bx, int bs, int H,
                                                 int W)
 {
@@ -153,16 +136,6 @@ __device__ uint8_t qpel_byte(const uint8_t *__restrict__ ref, const float *__res
     // taps with weight 0 are not read: they may lie outside the frame
     const uint32_t a = s[0], t1 = b.fx ? s[3] : 0u, t2 = b.fy ? s[rb] : 0u, t3 = (b.fx && b.fy) ? s[rb + 3] : 0u;
     return (uint8_t)bilinear(a, t1, t2, t3, b.fx, b.fy);
-}
-
-// bytes s .. s + 3 and s + 3 .. s + 6 of the frame out of the three aligned words that hold them
-__device__ __forceinline__ void seven_bytes(const uint8_t *__restrict__ ref, long long s, uint32_t &lo, uint32_t &hi)
-{
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(ref + (s & ~3LL));
-    const uint32_t o = (uint32_t)(s & 3);
-    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
-    lo = __builtin_amdgcn_alignbyte(w1, w0, o);
-    hi = __builtin_amdgcn_alignbyte(__builtin_amdgcn_alignbyte(w2, w1, o), lo, 3);
 }
 
 // Compensation: a thread makes 4 consecutive bytes of one output row (grid.y =

@@ -86,11 +86,32 @@ def block_matching(ref: np.ndarray, cur: np.ndarray, bs: int = 16, sr: int = 8, 
             b.free()
 
 
-def motion_compensate(frame: np.ndarray, mv: np.ndarray, bs: int = 16, subpel: int = 1) -> np.ndarray:
+OBMC_BLOCK_SIZES = (4, 8, 16, 32, 64)
+
+
+def check_obmc_bs(bs) -> int:
+    """The block sides of the overlapped compensator (include/vcf_amd.h)."""
+    if isinstance(bs, bool) or bs not in OBMC_BLOCK_SIZES:
+        raise ValueError(f"block size {bs!r} with obmc: 4, 8, 16, 32 or 64")
+    return int(bs)
+
+
+def mc_entry(subpel: int = 1, obmc: bool = False) -> str:
+    """The compensator of the C ABI for a precision and the obmc switch (one signature for all three)."""
+    if obmc:
+        return "vcf_ipp_motion_compensate_obmc"
+    return "vcf_ipp_motion_compensate_qpel" if subpel > 1 else "vcf_ipp_motion_compensate"
+
+
+def motion_compensate(frame: np.ndarray, mv: np.ndarray, bs: int = 16, subpel: int = 1, obmc: bool = False) -> np.ndarray:
     """IPP.motion_compensate (IPP_DCT.py:378-395); subpel > 1: the bilinear quarter-pel
-    compensator (vcf_ipp_motion_compensate_qpel), which rounds the field to quarter pels."""
+    compensator (vcf_ipp_motion_compensate_qpel), which rounds the field to quarter pels.
+    obmc: the overlapped compensator (vcf_ipp_motion_compensate_obmc; not in the reference) for
+    every subpel (a whole-pel field has zero fractions); bs must be 4, 8, 16, 32 or 64."""
     frame = _rgb(frame)
-    name = "vcf_ipp_motion_compensate_qpel" if _check_subpel(subpel) > 1 else "vcf_ipp_motion_compensate"
+    name = mc_entry(_check_subpel(subpel), obmc)
+    if obmc:
+        bs = check_obmc_bs(bs)
     H, W = frame.shape[:2]
     mv = np.ascontiguousarray(mv, np.float32)
     if mv.shape != (H // bs, W // bs, 2):
