@@ -589,6 +589,72 @@ int vcf_ipp_motion_compensate_qpel(const uint8_t *ref_rgb_dev, const float *mv_d
 int vcf_ipp_motion_compensate_obmc(const uint8_t *ref_rgb_dev, const float *mv_dev, int32_t H, int32_t W, int32_t bs,
                                    uint8_t *out_rgb_dev, void *stream);
 
+/* Coded motion fields (--mvc, --mv_lambda; not in the reference).  Integers
+ * throughout.  A vector is q = (qx, qy) in quarter pels, stored as float32
+ * q / 4 as above; step = 4 / subpel for subpel in {1, 2, 4}; a field F is
+ * nby x nbx = (H/bs) x (W/bs) vectors.  A float field entry becomes quarter
+ * pels as in the compensators: q = lrintf(4 m), clamped to +-2^28, a NaN gives
+ * -2^28.
+ * Predictor p(by, bx) of F: in the first row (by = 0) p = F[0, bx-1] if
+ * bx > 0, else (0, 0).  Below it p is the component-wise median of
+ *   A = F[by, bx-1] if bx > 0, else (0, 0);
+ *   B = F[by-1, bx];
+ *   C = F[by-1, bx+1] if bx + 1 < nbx, else F[by-1, bx-1] if bx > 0, else (0, 0).
+ * Bits: for an integer d, k = 2 d - 1 if d > 0, else -2 d, and
+ * len(d) = 2 floor(log2(k + 1)) + 1;
+ *   R(q, p) = len((qx - px) / step) + len((qy - py) / step),
+ * the division C's (truncating toward zero; exact for fields on the step grid).
+ * Coder (host code, vcf_mvc.cpp): vcf_mv_encode writes, block by block in
+ * raster order, the code of dx = (qx - px) / step, then of dy: signed
+ * exp-Golomb of order 0, that is floor(log2(k + 1)) zero bits, then k + 1 in
+ * binary.  Bits go MSB first; the last byte is padded with zero bits.  q holds
+ * nby * nbx * 2 int32 (x then y).  vcf_mv_decode inverts it block by block, the
+ * predictor reading vectors already decoded; the stream must be exactly the
+ * encoder's bytes.  vcf_mv_encode_bound gives a capacity that always suffices
+ * (70 bits per block).  VCF_ERR_INVALID: a null pointer, negative nby or nbx,
+ * step outside {1, 2, 4}, on encode |q| > 2^15 or q % step != 0 or a cap below
+ * the stream; on decode a stream that ends early, a prefix of more than 17
+ * zeros (|d| <= 2^16 needs no more), a decoded |q| > 2^15, non-zero padding or
+ * bytes after the last code.  Nothing is read or written out of bounds on a
+ * corrupt stream; on an error the contents of out / q are unspecified.
+ * Refinement (vcf_ipp_mv_refine, vcf_ipp_mvrefine.hip): `iterations` passes
+ * over the field at mv_dev, in and out.  One pass maps F_in to F_out and every
+ * block reads only F_in, so the result does not depend on scheduling.  For
+ * block (by, bx), with p its predictor from F_in, the candidates in index
+ * order are 0 the block's own vector, 1 p, 2 the left block's vector, 3 the
+ * top block's, 4 the right block's (by, bx+1), 5 the bottom block's
+ * (by+1, bx), 6 (0, 0).  A candidate whose neighbour lies outside the field is
+ * skipped; so is one that is invalid under "Sub-pel motion" (zero is always
+ * valid).  J = SAD + lambda R(c, p), with SAD the u8 luma of the reference,
+ * interpolated bilinearly at c, against the current luma, as in the sub-pel
+ * search; the winner is the argmin of (J, index).  J fits 32 bits:
+ * SAD <= 64*64*255, R <= 122, lambda <= 1024.  After the last pass the winners
+ * are written as float32 q / 4.
+ * Kernel: one launch per pass, one wave per block, the block's luma in LDS; a
+ * duplicate of a lower-indexed candidate is not evaluated (it cannot win the
+ * tie); where fx = fy = 0 the SAD runs on words (v_alignbyte + v_sad_u8, for
+ * bs % 4 == 0 and a 4-byte aligned workspace), else pixel by pixel.  The passes
+ * ping-pong between mv_dev and a second field in the workspace so that the
+ * last one writes mv_dev (an odd count starts with a copy into the workspace).
+ * Workspace (vcf_ipp_mv_refine_workspace_bytes): 2*H*W + 3 + 8 (H/bs)(W/bs)
+ * bytes -- the two gray planes as in vcf_ipp_block_match, then the second
+ * field at the first 4-byte aligned address at or after workspace_dev + 2*H*W.
+ * lambda in 0..1024, iterations in 1..4; limits and alignment as
+ * vcf_ipp_block_match_subpel: bs <= 64, mv_dev 4-byte aligned, the frames and
+ * the workspace unaligned; at most 65535 block rows.  VCF_ERR_INVALID before
+ * any device work for a violation, subpel outside {1, 2, 4}, workspace_bytes
+ * below the size function's, or a null pointer.  Written: the (H/bs) * (W/bs)
+ * * 2 floats at mv_dev, the 2*H*W gray bytes and the second field's
+ * 8 (H/bs)(W/bs) bytes; an empty field (H < bs or W < bs) is legal and writes
+ * nothing. */
+int vcf_mv_encode_bound(int32_t nby, int32_t nbx, int64_t *bytes);
+int vcf_mv_encode(const int32_t *q, int32_t nby, int32_t nbx, int32_t step, uint8_t *out, int64_t cap, int64_t *nbytes);
+int vcf_mv_decode(const uint8_t *in, int64_t nbytes, int32_t nby, int32_t nbx, int32_t step, int32_t *q);
+int vcf_ipp_mv_refine_workspace_bytes(int32_t H, int32_t W, int32_t bs, int64_t *bytes);
+int vcf_ipp_mv_refine(const uint8_t *ref_rgb_dev, const uint8_t *cur_rgb_dev, int32_t H, int32_t W, int32_t bs,
+                      int32_t subpel, int32_t lambda, int32_t iterations, float *mv_dev, uint8_t *workspace_dev,
+                      int64_t workspace_bytes, void *stream);
+
 /* residual_shifted = clip(cur - comp + 128, 0, 255) (IPP_DCT.py:547-551).  No
  * pointer needs alignment; writes the n bytes at out_dev. */
 int vcf_ipp_residual(const uint8_t *cur_dev, const uint8_t *comp_dev, int64_t n, uint8_t *out_dev, void *stream);

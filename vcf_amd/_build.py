@@ -25,13 +25,13 @@ AB_SOURCES = ["ab/vcf_dct_dz_ab.hip", "ab/vcf_dwt_ab.hip", "ab/vcf_dwt_sched.hip
 AB_LINK = ["vcf_runtime.hip", "vcf_dct_any.hip", "vcf_cbaac_gpu.hip", "vcf_cbaac.cpp", "vcf_ipp.hip", "vcf_dwt.hip"]
 SOURCES = ["vcf_runtime.hip", "vcf_dct_dz.hip", "vcf_dct_any.hip", "vcf_quant.hip", "vcf_dwt.hip", "vcf_cbaac.cpp",
            "vcf_cbahc.cpp", "vcf_ipp.hip", "vcf_ipp_rdo.hip", "vcf_ipp_subpel.hip", "vcf_ipp_hier.hip", "vcf_ipp_bipred.hip",
-           "vcf_ipp_obmc.hip", "vcf_png.cpp", "vcf_comm.cpp", "vcf_cbaac_gpu.hip", "vcf_plugins.hip", "vcf_deflate.hip",
+           "vcf_ipp_obmc.hip", "vcf_ipp_mvrefine.hip", "vcf_mvc.cpp", "vcf_png.cpp", "vcf_comm.cpp", "vcf_cbaac_gpu.hip", "vcf_plugins.hip", "vcf_deflate.hip",
            "vcf_inflate.hip", "vcf_mdct_dz.hip", "vcf_klt_dz.hip", "vcf_vq.hip", "vcf_lbt.hip",
            "vcf_distortion.hip", "vcf_ssim.hip", "vcf_index_hist.hip", "vcf_dct_rdoq.hip", "vcf_deblock.hip"]
 HEADERS = ["vcf_dct8.h", "vcf_dct_block.h", "vcf_dct_tile.h", "vcf_block_tile.h", "vcf_internal.h", "vcf_wavelets.h", "vcf_pocketfft.h", "vcf_pocketfft_tables.h",
            "vcf_pocketfft_rt.h", "vcf_pocketfft_blue.h", "vcf_sincos.h", "vcf_pipeline.h", "vcf_dwt_band.h", "vcf_idwt_line.h", "vcf_idwt_band21.h",
            "vcf_dwt_lift.h", "vcf_band_cut.h",
-           "vcf_deflate.h", "vcf_cbaac_coder.h", "vcf_ipp_qpel.h"]
+           "vcf_deflate.h", "vcf_cbaac_coder.h", "vcf_ipp_qpel.h", "vcf_mvc.h"]
 OBJDIR = os.path.join(ROOT, "build", "obj")
 ARCH = os.environ.get("VCF_OFFLOAD_ARCH", "gfx950")
 

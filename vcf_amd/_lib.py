@@ -148,6 +148,11 @@ SIGNATURES = {
     "vcf_ipp_motion_compensate_obmc": [_P, _P, _I32, _I32, _I32, _P, _P],
     "vcf_ipp_hier_workspace_bytes": [_I32, _I32, _I32, ctypes.POINTER(_I64)],
     "vcf_ipp_block_match_hier": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P],
+    "vcf_mv_encode_bound": [_I32, _I32, ctypes.POINTER(_I64)],
+    "vcf_mv_encode": [_P, _I32, _I32, _I32, _P, _I64, ctypes.POINTER(_I64)],
+    "vcf_mv_decode": [_P, _I64, _I32, _I32, _I32, _P],
+    "vcf_ipp_mv_refine_workspace_bytes": [_I32, _I32, _I32, ctypes.POINTER(_I64)],
+    "vcf_ipp_mv_refine": [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P],
     "vcf_ipp_residual": [_P, _P, _I64, _P, _P],
     "vcf_ipp_reconstruct": [_P, _P, _I64, _P, _P],
     "vcf_ipp_rdo_modes": [_P, _P, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _P, _P],

@@ -44,6 +44,15 @@ two included, by the overlapped one (vcf_amd/csrc/vcf_ipp_obmc.hip): a pixel is
 blended from its own block's vector and its nearest neighbours'.  -M must be 4,
 8, 16, 32 or 64; the searches, the motion file and the file names do not change;
 meta.json carries "obmc": true and the decoder compensates alike.
+--mvc (not in the reference) writes the motion file as {prefix}_mv.vmv instead
+of _mv.npz (vcf_amd/codec/mvfile.py): every field predicted from its neighbours
+by a median and coded with signed exp-Golomb codes (vcf_amd/csrc/vcf_mvc.cpp),
+the mode maps as one zlib stream; meta.json carries "mv_codec": "median-eg0" and
+the decoder dispatches on it.
+--mv_lambda L > 0 (not in the reference) re-decides every block's vector after
+every search by SAD + L * (that coder's bits), --mv_iters passes
+(vcf_amd/csrc/vcf_ipp_mvrefine.hip).  It changes only the vectors chosen; the
+decoder does not know of it.
 """
 from __future__ import annotations
 
@@ -57,8 +66,8 @@ import struct
 import numpy as np
 
 from .. import ipp as K
-from ..ipp import check_levels, check_obmc_bs, hier_workspace_bytes, mc_entry
-from . import shard
+from ..ipp import check_levels, check_mv_refine, check_obmc_bs, hier_workspace_bytes, mc_entry, mv_refine_workspace_bytes
+from . import mvfile, shard
 from .dct2d import CoDec as DCTCoDec
 from .dwt2d import CoDec as DWTCoDec
 from .eic import read_image, write_image
@@ -170,6 +179,14 @@ class _IPP:
                 check_obmc_bs(self.block_size_ME)
             except ValueError:
                 raise ValueError(f"--obmc with -M {self.block_size_ME}: -M must be 4, 8, 16, 32 or 64") from None
+        # the coded motion file (not in the reference); the decoder takes it from meta.json
+        self.mvc = bool(getattr(args, "mvc", False))
+        # rate-aware vector choice after every search (not in the reference); the encoder's choice alone
+        try:
+            self.mv_lambda, self.mv_iters = check_mv_refine(getattr(args, "mv_lambda", 0) or 0,
+                                                            getattr(args, "mv_iters", 2) or 2)
+        except ValueError as e:
+            raise ValueError(f"--mv_lambda / --mv_iters: {e}") from None
         self.prefix = resolve_prefix(args.output) if getattr(args, "output", None) else None
         self.group = group if group is not None else shard.Group()
 
@@ -181,6 +198,20 @@ class _IPP:
     # IPP_DCT.py:595-626: encode_fn to the frame's files, decode_fn back (in memory)
     def encode_decode_proxy(self, img, frame_type, seq_idx):
         return self._code_frame(img, f"{self.prefix}_{frame_type}_{seq_idx}_enc")
+
+    def _search(self, ref, cur, **kw):
+        """The motion search of cur in ref and, with --mv_lambda, the rate-aware refinement of its field."""
+        bs = self.block_size_ME
+        mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, **kw)
+        if self.mv_lambda:   # at 0 the calls are what they were
+            mv = K.refine_field(ref, cur, mv, bs, self.subpel, self.mv_lambda, self.mv_iters)
+        return mv
+
+    def _ws_bytes(self, H, W):
+        """The searches' workspace in the resident loops: the gray planes (and the pyramids), shared
+        with the refinement, whose second field overlays what the search no longer needs."""
+        n = hier_workspace_bytes(H, W, self.me_levels) if self.me_levels else 2 * H * W
+        return max(n, mv_refine_workspace_bytes(H, W, self.block_size_ME)) if self.mv_lambda else n
 
     def _gop(self, frames, g0, i_idx, p0):
         """One GOP: I-frame then P-frames (IPP.temporal_filter :397-575)."""
@@ -196,10 +227,10 @@ class _IPP:
             lv = {"levels": self.me_levels} if self.me_levels else {}   # at 0 the calls are what they were
             ob = {"obmc": True} if self.obmc else {}                    # and without --obmc
             if self.subpel > 1:
-                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, subpel=self.subpel, **lv)
+                mv = self._search(ref, cur, subpel=self.subpel, **lv)
                 comp = K.motion_compensate(ref, mv, bs, subpel=self.subpel, **ob)
             else:
-                mv = K.block_matching(ref, cur, bs, self.search_range, self.use_fast, **lv)
+                mv = self._search(ref, cur, **lv)
                 comp = K.motion_compensate(ref, mv, bs, **ob)
             if self.rdo_lambda > 0:
                 # :441-536: per-block I/P decision, the mixed-mode frame, its reconstruction
@@ -227,7 +258,7 @@ class _IPP:
     def _gop_bframes(self, frames, g0, i_idx, p0):
         """One GOP with B-frames: I, then per anchor interval the closing anchor (predicted from the
         anchor before it) and the B-frames between in display order (predicted from both)."""
-        bs, sr, fast = self.block_size_ME, self.search_range, self.use_fast
+        bs = self.block_size_ME
         kw = {"subpel": self.subpel} if self.subpel > 1 else {}
         sw = {**kw, "levels": self.me_levels} if self.me_levels else kw   # the searches' keywords
         cw = {**kw, "obmc": True} if self.obmc else kw                    # the compensations'
@@ -239,7 +270,7 @@ class _IPP:
         B = {"info": [], "mv": [], "modes": []}
         for a, c in _anchor_intervals(types):
             cur = frames[g0 + c]
-            mv = K.block_matching(recon[a], cur, bs, sr, fast, **sw)
+            mv = self._search(recon[a], cur, **sw)
             comp = K.motion_compensate(recon[a], mv, bs, **cw)
             rec_res, bits_P = self.encode_decode_proxy(K.residual(cur, comp), "P", p0 + len(P))
             recon[c] = K.reconstruct(comp, rec_res)
@@ -247,8 +278,8 @@ class _IPP:
             P.append({"bits": bits_P})
             for d in range(a + 1, c):
                 cur = frames[g0 + d]
-                mv_f = K.block_matching(recon[a], cur, bs, sr, fast, **sw)
-                mv_b = K.block_matching(recon[c], cur, bs, sr, fast, **sw)
+                mv_f = self._search(recon[a], cur, **sw)
+                mv_b = self._search(recon[c], cur, **sw)
                 cf = K.motion_compensate(recon[a], mv_f, bs, **cw)
                 cb = K.motion_compensate(recon[c], mv_b, bs, **cw)
                 modes, res = K.bipred_residual(cur, cf, cb, bs)
@@ -304,8 +335,13 @@ class _IPP:
                 B_infos.extend(rest[0] if rest else [])
         hb, wb = self.height // self.block_size_ME, self.width // self.block_size_ME
         mv = np.frombuffer(b"".join(mvs_all), np.float32).reshape(len(P_infos), hb, wb, 2)
-        mv_path = f"{self.prefix}_mv.npz"
-        if rdo:
+        mv_path = f"{self.prefix}_mv.vmv" if self.mvc else f"{self.prefix}_mv.npz"
+        if self.mvc:
+            mvfile.write(mv_path, mv, self.subpel,
+                         bmv=np.frombuffer(b"".join(bmv_all), np.float32).reshape(len(B_infos), 2, hb, wb, 2) if nb else None,
+                         modes=np.frombuffer(b"".join(modes_all), np.uint8).reshape(len(P_infos), hb, wb) if rdo else
+                         np.frombuffer(b"".join(bmodes_all), np.uint8).reshape(len(B_infos), hb, wb) if nb else None)
+        elif rdo:
             # the reference's entries are {"mv": field, "modes": map} (:529)
             modes = np.frombuffer(b"".join(modes_all), np.uint8).reshape(len(P_infos), hb, wb)
             obj = np.empty(len(P_infos), dtype=object)
@@ -327,7 +363,9 @@ class _IPP:
         self.total_bits = total_bits
         meta = {"n_frames": self.N_frames, "width": self.width, "height": self.height, "gop_size": self.gop_size,
                 "total_bits": total_bits, "I_info": I_infos, "P_info": P_infos,
-                "mv_file": f"{os.path.basename(self.prefix)}_mv.npz", "base_prefix": os.path.basename(self.prefix)}
+                "mv_file": os.path.basename(mv_path), "base_prefix": os.path.basename(self.prefix)}
+        if self.mvc:
+            meta["mv_codec"] = mvfile.CODEC   # the coded motion file: the decoder dispatches on it
         if self.subpel > 1:
             meta["subpel"] = self.subpel   # fractional vectors: the decoder must interpolate
         if self.obmc:
@@ -349,14 +387,7 @@ class _IPP:
         with open(f"{in_prefix}_meta.json") as f:
             meta = json.load(f)
         mv_path = f"{os.path.dirname(in_prefix)}/{meta['mv_file']}"
-        with np.load(mv_path, allow_pickle=False) as z:
-            if "mv_f32" not in z.files:
-                raise NotImplementedError(f"{mv_path}: motion fields stored only as a pickled object array "
-                                          "(written by the reference); re-encode or convert to 'mv_f32'")
-            mvs = z["mv_f32"]
-            modes = z["modes_u8"] if "modes_u8" in z.files else None
-            bmv = z["bmv_f32"] if "bmv_f32" in z.files else None
-            bmodes = z["bmodes_u8"] if "bmodes_u8" in z.files else None
+        mvs, modes, bmv, bmodes = self._read_motion(mv_path, meta)
         out_prefix = resolve_prefix(self.args.output)
         _ensure_dir(out_prefix)
         gop, N = meta["gop_size"], meta["n_frames"]
@@ -389,6 +420,29 @@ class _IPP:
                 recon.append(ref)
                 p_idx += 1
         return self._write_decoded(out_prefix, recon)
+
+    def _read_motion(self, mv_path, meta):
+        """(P fields, -R mode maps or None, B fields or None, B mode maps or None) of the motion file,
+        by meta.json's "mv_codec": absent, the .npz; "median-eg0", the coded file (mvfile.py)."""
+        codec = meta.get("mv_codec")
+        if codec is None:
+            with np.load(mv_path, allow_pickle=False) as z:
+                if "mv_f32" not in z.files:
+                    raise NotImplementedError(f"{mv_path}: motion fields stored only as a pickled object array "
+                                              "(written by the reference); re-encode or convert to 'mv_f32'")
+                return (z["mv_f32"], z["modes_u8"] if "modes_u8" in z.files else None,
+                        z["bmv_f32"] if "bmv_f32" in z.files else None,
+                        z["bmodes_u8"] if "bmodes_u8" in z.files else None)
+        if codec != mvfile.CODEC:
+            raise NotImplementedError(f"meta.json: mv_codec {codec!r} ({mvfile.CODEC!r} or absent)")
+        f = mvfile.read(mv_path)
+        bs = self.block_size_ME
+        n_b = len(meta.get("B_info", [])) if "bframes" in meta else 0
+        mvfile.check_header(f, int(meta["height"]) // bs, int(meta["width"]) // bs, int(meta.get("subpel", 1)),
+                            len(meta["P_info"]), n_b)
+        if n_b:
+            return f["mv_f32"], None, f["bmv_f32"], f["modes"]
+        return f["mv_f32"], f["modes"], None, None
 
     def _decode_bframes(self, meta, in_prefix, mvs, bmv, bmodes, subpel, obmc=False):
         """The frames of a --bframes stream in display order: per GOP the I-frame, then per anchor
@@ -481,7 +535,7 @@ class CoDec(_IPP, DCTCoDec):
         n_b = self._b0(g0)
         s = Stream()
         cur, past, future, cf, cb, res, rec = (DeviceBuffer(n) for _ in range(7))
-        nws = hier_workspace_bytes(H, W, self.me_levels) if self.me_levels else 2 * H * W
+        nws = self._ws_bytes(H, W)
         dk, dgray = DeviceBuffer(Hp * Wp * 3), DeviceBuffer(nws)
         dmv, dmv_b, dmodes = DeviceBuffer(max(1, hb * wb * 8)), DeviceBuffer(max(1, hb * wb * 8)), \
             DeviceBuffer(max(1, hb * wb))
@@ -516,6 +570,9 @@ class CoDec(_IPP, DCTCoDec):
                      dgray.ptr, sh)
             else:
                 call("vcf_ipp_block_match", ref.ptr, cur.ptr, H, W, bs, sr, fast, field.ptr, dgray.ptr, sh)
+            if self.mv_lambda:
+                call("vcf_ipp_mv_refine", ref.ptr, cur.ptr, H, W, bs, self.subpel, self.mv_lambda, self.mv_iters,
+                     field.ptr, dgray.ptr, nws, sh)
             call(mc_entry(self.subpel, self.obmc), ref.ptr, field.ptr, H, W, bs, comp.ptr, sh)
             mv = np.zeros((hb, wb, 2), np.float32)
             if mv.size:
@@ -572,7 +629,7 @@ class CoDec(_IPP, DCTCoDec):
         hb, wb = H // bs, W // bs
         s = Stream()
         cur, ref, comp, res, rec = (DeviceBuffer(n) for _ in range(5))
-        nws = hier_workspace_bytes(H, W, self.me_levels) if self.me_levels else 2 * H * W
+        nws = self._ws_bytes(H, W)
         dk, dmv, dgray = DeviceBuffer(Hp * Wp * 3), DeviceBuffer(max(1, hb * wb * 8)), DeviceBuffer(nws)
         dmodes = DeviceBuffer(max(1, hb * wb))
         q, flags, B = self.QSS, self.flags, self.block_size
@@ -612,6 +669,9 @@ class CoDec(_IPP, DCTCoDec):
                     else:
                         call("vcf_ipp_block_match", ref.ptr, cur.ptr, H, W, bs, int(self.search_range),
                              int(bool(self.use_fast)), dmv.ptr, dgray.ptr, sh)
+                    if self.mv_lambda:
+                        call("vcf_ipp_mv_refine", ref.ptr, cur.ptr, H, W, bs, self.subpel, self.mv_lambda,
+                             self.mv_iters, dmv.ptr, dgray.ptr, nws, sh)
                     call(mc_entry(self.subpel, self.obmc), ref.ptr, dmv.ptr, H, W, bs, comp.ptr, sh)
                     mv = np.zeros((hb, wb, 2), np.float32)
                     if mv.size:

@@ -49,23 +49,26 @@ class _At:
 class DeviceIPP:
     """One rank's part of a GOP-sharded, HBM-resident IPP encode (2D-DCT,
     deadzone Q, the reference's default -c TIFF), full search or --fast, or the
-    hierarchical search (levels > 0); obmc: the overlapped compensator (bs 4, 8, 16, 32 or 64)."""
+    hierarchical search (levels > 0); obmc: the overlapped compensator (bs 4, 8, 16, 32 or 64);
+    mv_lambda > 0: the rate-aware refinement of every field (vcf_ipp_mv_refine), mv_iters passes."""
 
     def __init__(self, comm, rank: int, world: int, n_frames: int, H: int, W: int, Q: int = 32, gop: int = 10,
                  bs: int = 16, sr: int = 8, fast: bool = False, subpel: int = 1, levels: int = 0,
-                 obmc: bool = False):
+                 obmc: bool = False, mv_lambda: int = 0, mv_iters: int = 2):
         self.comm, self.rank, self.world = comm, int(rank), int(world)
         self.N, self.H, self.W, self.Q = int(n_frames), int(H), int(W), int(Q)
         self.gop, self.bs, self.sr, self.fast = int(gop), int(bs), int(sr), bool(fast)
         if subpel not in (1, 2, 4):
             raise ValueError(f"subpel {subpel!r}: 1, 2 or 4")
         self.subpel = int(subpel)   # > 1: half / quarter-pel vectors and the bilinear compensator
-        from ..ipp import check_levels, check_obmc_bs, hier_workspace_bytes, mc_entry
+        from ..ipp import check_levels, check_mv_refine, check_obmc_bs, hier_workspace_bytes, mc_entry, \
+            mv_refine_workspace_bytes
         self.levels = check_levels(levels, self.bs, self.fast)   # > 0: the hierarchical search
         self.obmc = bool(obmc)
         if self.obmc:
             check_obmc_bs(self.bs)
         self.mc = mc_entry(self.subpel, self.obmc)   # the compensator's entry point
+        self.mv_lambda, self.mv_iters = check_mv_refine(mv_lambda, mv_iters)
         self.n_gops = (self.N + self.gop - 1) // self.gop
         self.g_lo, self.g_hi = frame_range(self.n_gops, self.rank, self.world)
 
@@ -97,6 +100,8 @@ class DeviceIPP:
         self.mvb = self.hb * self.wb * 8
         self.mv = DeviceBuffer(max(1, max(1, self.n_local) * self.mvb))
         self.gray_bytes = hier_workspace_bytes(self.H, self.W, self.levels) if self.levels else 2 * self.H * self.W
+        if self.mv_lambda:   # the refinement shares the workspace: its field overlays what the search is done with
+            self.gray_bytes = max(self.gray_bytes, mv_refine_workspace_bytes(self.H, self.W, self.bs))
         self.gray = DeviceBuffer(self.gray_bytes)
         self.out = DeviceBuffer(max(1, self.n_local * self.spf * self.slot))
         self.sizes = DeviceBuffer(max(4, self.n_local * self.spf * 4))
@@ -148,6 +153,9 @@ class DeviceIPP:
                 else:
                     call("vcf_ipp_block_match", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.sr, int(self.fast),
                          mv.ptr, self.gray.ptr, sh)
+                if self.mv_lambda:
+                    call("vcf_ipp_mv_refine", ref.ptr, cur.ptr, self.H, self.W, self.bs, self.subpel, self.mv_lambda,
+                         self.mv_iters, mv.ptr, self.gray.ptr, self.gray_bytes, sh)
                 call(self.mc, ref.ptr, mv.ptr, self.H, self.W, self.bs, comp.ptr, sh)
                 call("vcf_ipp_residual", cur.ptr, comp.ptr, fb, self.res.address(j * fb), sh)
                 p_frames.append(f)

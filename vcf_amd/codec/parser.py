@@ -616,6 +616,16 @@ def add_ipp(enc, dec):
                      help="Overlapped block motion compensation: blend each pixel from its own block's vector and its "
                           "nearest neighbours' (default: off; not in the reference, whose decoder cannot decode such "
                           "streams; -M must be 4, 8, 16, 32 or 64)")
+    enc.add_argument("--mvc", action="store_true",
+                     help="Write the motion file coded (_mv.vmv: median prediction from the neighbours, signed "
+                          "exp-Golomb codes) instead of the deflated _mv.npz (default: off; not in the reference, "
+                          "whose decoder cannot read such streams)")
+    enc.add_argument("--mv_lambda", type=int, default=0, metavar="L",
+                     help="Re-decide every block's vector after every motion search by SAD + L * (bits of the coded "
+                          "motion file), 0 .. 1024 (default: 0, off; not in the reference, whose decoder still "
+                          "decodes such streams)")
+    enc.add_argument("--mv_iters", type=int, choices=range(1, 5), default=2, metavar="K",
+                     help="Passes of the --mv_lambda refinement, 1 .. 4 (default: 2)")
     dec.add_argument("-i", "--input", type=str, default=IPP_OUTPUT, help=f"Input prefix (default: {IPP_OUTPUT})")
     dec.add_argument("-O", "--output", type=str, default="./ipp_decoded", help="Output prefix (default: ./ipp_decoded)")
     dec.add_argument("-N", "--number_of_frames", type=int, default=IPP_N_FRAMES,

@@ -261,3 +261,82 @@ def bipred_reconstruct(cf: np.ndarray, cb: np.ndarray, modes: np.ndarray, rec: n
     finally:
         for x in (df, db, dr, do, dm):
             x.free()
+
+
+def check_mv_refine(lam, iterations):
+    """The limits of vcf_ipp_mv_refine (include/vcf_amd.h): lambda 0 .. 1024, 1 .. 4 iterations."""
+    if isinstance(lam, bool) or not isinstance(lam, (int, np.integer)) or not 0 <= lam <= 1024:
+        raise ValueError(f"mv lambda {lam!r}: an integer 0 .. 1024")
+    if isinstance(iterations, bool) or iterations not in (1, 2, 3, 4):
+        raise ValueError(f"mv iterations {iterations!r}: 1 .. 4")
+    return int(lam), int(iterations)
+
+
+def mv_refine_workspace_bytes(H: int, W: int, bs: int) -> int:
+    """vcf_ipp_mv_refine_workspace_bytes: the two gray planes and a second field."""
+    import ctypes
+    n = ctypes.c_int64(0)
+    L.call("vcf_ipp_mv_refine_workspace_bytes", int(H), int(W), int(bs), ctypes.byref(n))
+    return int(n.value)
+
+
+def refine_field(ref: np.ndarray, cur: np.ndarray, mv: np.ndarray, bs: int, subpel: int = 1, lam: int = 0,
+                 iterations: int = 2) -> np.ndarray:
+    """vcf_ipp_mv_refine (not in the reference): every block re-decides its vector among its own, the
+    motion coder's predictor, its four neighbours' and zero by SAD + lam * bits -> the new field."""
+    ref, cur = _rgb(ref), _rgb(cur)
+    if ref.shape != cur.shape:
+        raise ValueError("shape mismatch")
+    subpel = _check_subpel(subpel)
+    lam, iterations = check_mv_refine(lam, iterations)
+    bs = _check_bs(bs)
+    H, W = ref.shape[:2]
+    mv = np.ascontiguousarray(mv, np.float32)
+    if mv.shape != (H // bs, W // bs, 2):
+        raise ValueError(f"motion field shape {mv.shape} != {(H // bs, W // bs, 2)}")
+    if mv.size == 0:
+        return mv.copy()
+    nws = mv_refine_workspace_bytes(H, W, bs)
+    dr, dc, dm, dw = DeviceBuffer.from_array(ref), DeviceBuffer.from_array(cur), DeviceBuffer.from_array(mv), \
+        DeviceBuffer(nws)
+    try:
+        L.call("vcf_ipp_mv_refine", dr.ptr, dc.ptr, H, W, bs, subpel, lam, iterations, dm.ptr, dw.ptr, nws, None)
+        return dm.download(np.empty_like(mv))
+    finally:
+        for b in (dr, dc, dm, dw):
+            b.free()
+
+
+def _field_q(q) -> np.ndarray:
+    q = np.asarray(q)
+    if q.ndim != 3 or q.shape[2] != 2 or q.dtype.kind not in "iu":
+        raise ValueError("expected an nby x nbx x 2 integer field (quarter pels)")
+    if q.size and int(np.abs(q.astype(np.int64)).max()) > 1 << 15:
+        raise ValueError("vector component beyond +-2^15 quarter pels")
+    return np.ascontiguousarray(q, np.int32)
+
+
+def mv_encode(q: np.ndarray, step: int = 1) -> bytes:
+    """vcf_mv_encode (host code): an nby x nbx x 2 integer field of quarter-pel vectors on the step
+    grid (step = 4 / subpel) -> median-predicted signed exp-Golomb codes."""
+    import ctypes
+    q = _field_q(q)
+    nby, nbx = q.shape[:2]
+    cap = ctypes.c_int64(0)
+    L.call("vcf_mv_encode_bound", nby, nbx, ctypes.byref(cap))
+    out, n = np.empty(max(1, cap.value), np.uint8), ctypes.c_int64(0)
+    L.call("vcf_mv_encode", q.ctypes.data if q.size else out.ctypes.data, nby, nbx, int(step), out.ctypes.data,
+           cap.value, ctypes.byref(n))
+    return out[:n.value].tobytes()
+
+
+def mv_decode(data: bytes, nby: int, nbx: int, step: int = 1) -> np.ndarray:
+    """vcf_mv_decode: the inverse -> (nby, nbx, 2) int32; ValueError for a stream the encoder does not write."""
+    if nby < 0 or nbx < 0:
+        raise ValueError(f"motion field of {nby} x {nbx} blocks")
+    buf = np.frombuffer(bytes(data), np.uint8)
+    src = buf if buf.size else np.zeros(1, np.uint8)
+    q = np.zeros((int(nby), int(nbx), 2), np.int32)
+    L.call("vcf_mv_decode", src.ctypes.data, buf.size, int(nby), int(nbx), int(step),
+           q.ctypes.data if q.size else src.ctypes.data)
+    return q
